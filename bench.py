@@ -18,7 +18,15 @@ Multi-GPU (weak scaling): one process per GPU (torch.distributed.run
 launches them; nothing here imports torch), chains sharded by global id with
 no collective in the data path; rank 0 hands its ncclUniqueId to the others
 over TCP (stdlib), barriers and the max-over-ranks time are RCCL all-reduces,
-and ONE RCCL all-gather collects the per-chain statistics (timed separately).
+and ONE RCCL all-gather collects the per-chain statistics (timed separately;
+--full only).
+
+A plain run sets up, warms up, times the --steps steps, writes the last
+step's records when --dump-outputs is given, and prints the result line.
+Everything else the line can carry takes --full: the CPU baseline, the
+launched-form (PBH_SERVER=0) and REPLAY rates on fresh engines, the
+statistics all-gather with its every-chain-once check, and the look-up of
+the measured HBM traffic under profiles/.
 """
 import argparse
 import json
@@ -36,6 +44,7 @@ if ROOT not in sys.path:
 METRIC = ('MH chain-steps/sec (whole node), 10-dim model, 65 536 chains, '
           '1/2/4/8 GPU')
 D = 10
+SEED = 20261015         # the RNG seed of every run: the same chains each time
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
 
@@ -226,7 +235,7 @@ class EngineCollective:
 
 
 def run_rank(eng, col, rank, world, chains_per_gpu, steps, warmup, spl, rng,
-             trace=True, moments=False, seed=20261015, warmup_spl=None,
+             trace=True, moments=False, seed=SEED, warmup_spl=None,
              gather=True):
   """One rank of the bench (weak scaling: chains_per_gpu chains per rank):
   shard the global chain ids, warm up, time exactly `steps` steps between
@@ -366,6 +375,42 @@ def run_replay_rank(make_engine, col, rank, world, chains_per_gpu, steps, warmup
   return float(chains_per_gpu) * world * steps / el, el
 
 
+DUMP_MAX_BYTES = 64 << 20   # all files of one --dump-outputs, every rank's
+
+
+def dump_outputs(eng, path, rank, world, last, trace=True):
+  """What the timed run left for its caller, of its LAST step, as
+  path/<name>.npy (rank 0; <name>_rank<r>.npy on the others).  With the
+  trace: record `last` of Engine.trace() -- x [N, d] and logp [N] (float64)
+  and the accept bit as accept [N] (float32).  Without it (--no-trace) the
+  chain state Engine.state() holds after that step (x, logp) and the running
+  moments (sum, sumsq [N, d], float64; n_acc [N] as float64).  Chains past
+  the size limit (DUMP_MAX_BYTES over all ranks) are cut to a fixed seeded
+  sample, its chain indices kept in order; returns {name: shape}."""
+  if trace:
+    rec = eng.trace(first=last, count=1)
+    arrs = {'x': rec['v_x'][:, 0, :], 'logp': rec['v_p'][:, 0],
+            'accept': np.asarray(rec['u'][:, 0], np.float32)}
+  else:
+    x, lp = eng.state()
+    mom = eng.moments()
+    arrs = {'x': x, 'logp': lp, 'sum': mom['sum'], 'sumsq': mom['sumsq'],
+            'n_acc': np.asarray(mom['n_acc'], np.float64)}
+  arrs = {k: np.ascontiguousarray(v, np.float32 if v.dtype == np.float32
+                                  else np.float64) for k, v in arrs.items()}
+  n = len(arrs['x'])
+  row_bytes = sum(v.nbytes for v in arrs.values()) // max(n, 1)
+  keep = (DUMP_MAX_BYTES // world - 1024 * len(arrs)) // max(row_bytes, 1)
+  if n > keep:
+    idx = np.sort(np.random.RandomState(SEED).choice(n, keep, replace=False))
+    arrs = {k: v[idx] for k, v in arrs.items()}
+  os.makedirs(path, exist_ok=True)
+  suffix = '' if rank == 0 else '_rank{}'.format(rank)
+  for k, v in arrs.items():
+    np.save(os.path.join(path, k + suffix + '.npy'), v)
+  return {k: list(v.shape) for k, v in arrs.items()}
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--gpus', type=int, default=1)
@@ -381,6 +426,15 @@ def main():
   ap.add_argument('--moments', action='store_true',
                   help='keep in-kernel running moments (off: the trace is '
                   'reduced on the device after the timed region)')
+  ap.add_argument('--full', action='store_true',
+                  help='also run what the headline does not need: the CPU '
+                  'baseline, the launched-form and REPLAY rates, the '
+                  'statistics all-gather and its check, the measured-traffic '
+                  'look-up (each can still be dropped by its --no-* option)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps write the records of the last '
+                  'timed step (x, logp, accept; the state and moments with '
+                  '--no-trace) as DIR/<name>.npy')
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--warmup-spl', type=int, default=None,
                   help='steps per warm-up launch (default: 1 for a warm-up '
@@ -404,7 +458,7 @@ def main():
   # at world > 1 the other ranks wait for it at the ncclUniqueId hand-off
   # (exchange_unique_id), so every SCALE line carries the baseline too
   cpu = None
-  if rank == 0 and not args.no_cpu_baseline:
+  if args.full and rank == 0 and not args.no_cpu_baseline:
     cpu = cpu_baseline()
 
   sha = lib_sha256()   # the binary the line (and its traffic profile) is of
@@ -433,11 +487,16 @@ def main():
   spl = args.steps_per_launch
   res = run_rank(eng, col, rank, world, args.chains, args.steps, args.warmup,
                  spl, args.rng, trace=not args.no_trace, moments=args.moments,
-                 warmup_spl=args.warmup_spl)
+                 warmup_spl=args.warmup_spl, gather=args.full)
   n, el, kern_ms, launches = res['n'], res['el'], res['kern_ms'], res['launches']
   srv = bool(res.get('server') and res['server'].get('commands'))
+  dumped = None
+  if args.dump_outputs:
+    # the last timed step, before anything else runs on this device
+    dumped = dump_outputs(eng, args.dump_outputs, rank, world,
+                          args.warmup + args.steps - 1, trace=not args.no_trace)
   launched = None
-  if srv and not args.no_launched:
+  if args.full and srv and not args.no_launched:
     # the same shape launched per run (the engine's default form), after the
     # headline: reported beside value, never folded into it
     launched = run_launched_rank(lambda: Engine(cfg2_spec(), device=local), col,
@@ -445,7 +504,7 @@ def main():
                                  args.warmup, spl, args.rng, not args.no_trace,
                                  args.moments, args.warmup_spl)
   replay = None
-  if not args.no_replay:
+  if args.full and not args.no_replay:
     # after the headline's timed region and its collection, on a fresh engine
     replay = run_replay_rank(lambda: Engine(cfg2_spec(), device=local), col, rank,
                              world, args.chains, args.steps, args.warmup,
@@ -481,7 +540,8 @@ def main():
                      'traffic': args.traffic_bytes if args.traffic_bytes
                                 else measured_traffic(
                                     n, min(spl, args.steps), args.rng,
-                                    not args.no_trace, sha, srv=srv),
+                                    not args.no_trace, sha, srv=srv)
+                                if args.full else None,
                      'bytes_per_chain_step': bpcs,
                      'kernel': kernel_label(args, n, srv),
                      'avg_launch_ms': avg_launch_s * 1e3,
@@ -501,6 +561,8 @@ def main():
         'host_us': (el - kern_ms / 1e3) * 1e6,
         'lib_sha256': sha,
     }
+    if dumped is not None:
+      line['dumped'] = dumped
     if collect_ms is not None:
       line['rccl_allgather_ms'] = collect_ms
     if launched is not None:

@@ -8,7 +8,8 @@ timeout -k 10 400 python -u -m pytest tests -m gpu -q -rf -p no:warnings --timeo
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/${TAG}_smoke.log 2>&1 || exit $?
 timeout -k 10 300 python scripts/bench_workloads.py --no-cpu-baseline > gpurun_out/${TAG}_wl.jsonl 2>&1 || exit $?
 bash scripts/profile_r04.sh || exit $?
+mkdir -p ${OUT:-bench_out}
 for i in 1 2 3; do
-  timeout -k 10 120 python bench.py --steps 20 --warmup 5 >> gpurun_out/${TAG}_s20_lines.jsonl 2>&1 || exit $?
+  timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 >> ${OUT:-bench_out}/${TAG}_s20_lines.jsonl 2>&1 || exit $?
 done
 bash scripts/gpu_legacy_pmc.sh ${TAG}_leg

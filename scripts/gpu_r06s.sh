@@ -13,7 +13,7 @@ tail -1 $OUT/tests.log > $OUT/tests_summary.txt
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1 || exit $?
 timeout -k 10 120 python scripts/server_probe.py 65536 20 > $OUT/probe.jsonl 2>&1 || exit $?
 timeout -k 10 300 python scripts/bench_workloads.py --no-cpu-baseline --only cfg5 > $OUT/cfg5.jsonl 2>&1 || exit $?
-timeout -k 10 300 python bench.py > $OUT/bench_default.jsonl 2> $OUT/bench_default.err || exit $?
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver.jsonl 2> $OUT/bench_driver.err || exit $?
+timeout -k 10 300 python bench.py --full > $OUT/bench_default.jsonl 2> $OUT/bench_default.err || exit $?
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.jsonl 2> $OUT/bench_driver.err || exit $?
 timeout -k 10 200 python scripts/facade_workload.py 65536 1000 3 250 > $OUT/facade_workload.jsonl 2>&1 || exit $?
 timeout -k 10 200 python scripts/setup_probe.py > $OUT/setup_probe.jsonl 2>&1 || exit $?

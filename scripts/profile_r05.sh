@@ -19,12 +19,12 @@ rm -rf $OUT && mkdir -p $OUT
 sha256sum probayes_amd/libpbhip.so > $OUT/lib.sha256
 cd /tmp
 mkdir -p $OUT/s20srv
-timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s20srv/trace -o run -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-replay > $OUT/s20srv/bench_trace.log 2>&1
-for i in 1 2 3; do timeout -k 10 200 python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-replay >> $OUT/s20srv/bench.log 2>&1; done
+timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s20srv/trace -o run -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-replay > $OUT/s20srv/bench_trace.log 2>&1
+for i in 1 2 3; do timeout -k 10 200 python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-replay >> $OUT/s20srv/bench.log 2>&1; done
 timeout -k 10 120 python3 $R/scripts/server_probe.py 65536 20 > $OUT/s20srv/probe.jsonl 2>&1
 for S in s20 s1000; do
   mkdir -p $OUT/$S
-  if [ $S = s20 ]; then ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-replay"; else ARGS="--steps 1000 --warmup 250 --no-cpu-baseline --no-replay"; fi
+  if [ $S = s20 ]; then ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-replay"; else ARGS="--full --steps 1000 --warmup 250 --no-cpu-baseline --no-replay"; fi
   export PBH_SERVER=0
   timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$S/trace -o run -- python3 $R/bench.py $ARGS > $OUT/$S/bench_trace.log 2>&1
   timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/$S/fetch -o run -- python3 $R/bench.py $ARGS > $OUT/$S/bench_fetch.log 2>&1
@@ -34,5 +34,5 @@ for S in s20 s1000; do
   unset PBH_SERVER
 done
 cd $R
-timeout -k 10 300 python3 bench.py > $OUT/bench_default.log 2>&1
-timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver.log 2>&1
+timeout -k 10 300 python3 bench.py --full > $OUT/bench_default.log 2>&1
+timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.log 2>&1

@@ -34,7 +34,7 @@ step $OUT/s20srv/bench_trace.log 200 rocprofv3 --kernel-trace --stats --output-f
 step $OUT/s20srv/bench_fetch.log 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/s20srv/fetch -o run -- python3 $R/bench.py --steps 20 --warmup 5 $BA
 step $OUT/s20srv/bench_write.log 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/s20srv/write -o run -- python3 $R/bench.py --steps 20 --warmup 5 $BA
 step $OUT/s20srv/bench_sq.log 120 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d $OUT/s20srv/sq -o run -- python3 $R/bench.py --steps 20 --warmup 5 $BA
-for i in 1 2 3; do step $OUT/s20srv/bench_$i.log 200 python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-replay; done
+for i in 1 2 3; do step $OUT/s20srv/bench_$i.log 200 python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-replay; done
 step $OUT/s20srv/probe.jsonl 120 python3 $R/scripts/server_probe.py 65536 20
 for S in s20 s1000; do
   mkdir -p $OUT/$S
@@ -48,5 +48,5 @@ for S in s20 s1000; do
   unset PBH_SERVER
 done
 cd $R
-step $OUT/bench_default.log 300 python3 bench.py
-step $OUT/bench_driver.log 200 python3 bench.py --steps 20 --warmup 5
+step $OUT/bench_default.log 300 python3 bench.py --full
+step $OUT/bench_driver.log 200 python3 bench.py --full --steps 20 --warmup 5

@@ -278,7 +278,7 @@ def test_failure_vote_survives_a_nan_dropping_max():
   assert 'a rank could not take part' in vote_message('x', fill)
 
 
-MAIN_WORKER = ENGINE_STANDIN + r'''
+MAIN_ENGINE = ENGINE_STANDIN + r'''
 import functools, io, json, contextlib
 import bench
 import probayes_amd
@@ -322,6 +322,12 @@ class MainEngine(OracleEngine):
     return {{'active': False, 'commands': 1, 'launches': 1}}
   def stop_server(self):
     pass
+  def trace(self, first=0, count=None):
+    n = len(self.x0)
+    seeds = self.seed + self.off + np.arange(n)
+    out = oracle.run_mh(self.spec, self.x0,
+                        oracle.legacy_streams(self.spec, seeds, self.done))
+    return {{k: out[k][:, first:first + count] for k in ('v_x', 'v_p', 'u')}}
   def close(self):
     if getattr(self, 'col', None) is not None:
       self.col.close()
@@ -329,10 +335,13 @@ class MainEngine(OracleEngine):
 
 probayes_amd.Engine = MainEngine        # main() imports it from the package
 bench.lib_sha256 = lambda: 'standin'    # no library file needed on CPU
+'''
+
+MAIN_WORKER = MAIN_ENGINE + r'''
 bench.cpu_baseline = functools.partial(bench.cpu_baseline, budget_s=0.3,
                                        chains=256)
 sys.argv = ['bench.py', '--gpus', str(world), '--steps', '12', '--warmup',
-            '5', '--chains', '6', '--steps-per-launch', '4']
+            '5', '--chains', '6', '--steps-per-launch', '4', '--full']
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
   bench.main()
@@ -370,6 +379,94 @@ def test_two_rank_bench_main_prints_one_scale_line(tmp_path):
   script.write_text(MAIN_WORKER.format(root=ROOT))
   outs = _spawn(script, 2, _free_port())
   assert 'MAIN_OK' in outs[0] and 'QUIET_OK' in outs[1], outs
+
+
+PLAIN_WORKER = MAIN_ENGINE + r'''
+def forbidden(*a, **k):
+  raise AssertionError('a plain run does only what its headline needs')
+bench.cpu_baseline = bench.run_launched_rank = bench.run_replay_rank = forbidden
+bench.measured_traffic = forbidden
+dump = {dump!r}
+lines = []
+for _ in range(2):
+  sys.argv = ['bench.py', '--gpus', '1', '--steps', '12', '--warmup', '5',
+              '--chains', '6', '--steps-per-launch', '4', '--dump-outputs', dump]
+  buf = io.StringIO()
+  with contextlib.redirect_stdout(buf):
+    bench.main()
+  out = [l for l in buf.getvalue().splitlines() if l.strip()]
+  assert len(out) == 1, out
+  line = json.loads(out[0])
+  lines.append(line)
+  got = {{f[:-4]: np.load(os.path.join(dump, f)) for f in sorted(os.listdir(dump))}}
+  assert sorted(got) == ['accept', 'logp', 'x'], sorted(got)
+  assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+  assert got['x'].shape == (6, bench.D) and got['logp'].shape == (6,)
+  assert got['accept'].shape == (6,)
+  # the last timed step (record 5 + 12 - 1) of the stand-in's own trace
+  ref = MainEngine(bench.cfg2_spec())
+  ref.init_chains(np.zeros((6, bench.D)), 0)
+  ref.set_rng('philox', bench.SEED)
+  ref.alloc_trace(17)
+  ref.run(17)
+  rec = ref.trace(16, 1)
+  assert np.array_equal(got['x'], rec['v_x'][:, 0]), 'x'
+  assert np.array_equal(got['logp'], rec['v_p'][:, 0]), 'logp'
+  assert np.array_equal(got['accept'], rec['u'][:, 0]), 'accept'
+  assert line['dumped'] == {{'x': [6, bench.D], 'logp': [6], 'accept': [6]}}, line
+line = lines[0]
+assert line['steps'] == 12 and line['warmup'] == 5 and line['n_gpus'] == 1
+assert line['unit'] == 'chain-steps/s' and line['higher_is_better'] is True
+assert line['dtype'] == 'f64' and line['metric'] == bench.METRIC
+assert abs(line['value'] * line['ms_per_step'] * 12 / 1e3 / (6 * 12) - 1) < 1e-9
+for k in ('cpu_baseline', 'launched', 'launched_chain_steps_per_s',
+          'replay_chain_steps_per_s', 'rccl_allgather_ms'):
+  assert k not in line, k
+assert line['roofline']['traffic'] is None
+print('PLAIN_OK')
+'''
+
+
+def test_plain_bench_main_runs_only_the_headline_and_dumps_its_last_step(tmp_path):
+  """bench.main() without --full on one rank (the engine stand-in): no CPU
+  baseline, launched-form, REPLAY or traffic look-up runs and none of their
+  fields is in the line, whose headline fields are there; --dump-outputs
+  writes the last timed step's records (x, logp, accept) as float arrays,
+  equal to the stand-in's own trace and the same on a second run."""
+  script = tmp_path / 'plain.py'
+  script.write_text(PLAIN_WORKER.format(root=ROOT, dump=str(tmp_path / 'dump')))
+  env = dict(os.environ, WORLD_SIZE='1', RANK='0', LOCAL_RANK='0')
+  p = subprocess.run([sys.executable, str(script)], env=env, text=True,
+                     stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                     timeout=240)
+  assert p.returncode == 0 and 'PLAIN_OK' in p.stdout, p.stdout
+
+
+def test_dump_outputs_keeps_a_fixed_sample_within_the_size_limit(tmp_path,
+                                                                 monkeypatch):
+  """A dump larger than the limit is cut to a seeded sample of chains (the
+  same rows of every array, the same on every call), within the limit."""
+  import bench
+
+  class Eng:
+    def trace(self, first, count):
+      n = 5000
+      x = np.arange(n * bench.D, dtype=float).reshape(n, 1, bench.D)
+      return {'v_x': x, 'v_p': x[:, :, 0] * 2., 'u': (np.arange(n) % 2)[:, None]}
+
+  monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 100000)
+  shapes = bench.dump_outputs(Eng(), str(tmp_path / 'a'), 0, 1, 7)
+  bench.dump_outputs(Eng(), str(tmp_path / 'b'), 0, 1, 7)
+  a = {k: np.load(str(tmp_path / 'a' / (k + '.npy'))) for k in shapes}
+  total = sum(os.path.getsize(str(tmp_path / 'a' / f))
+              for f in os.listdir(str(tmp_path / 'a')))
+  assert total <= 100000 and 900 < len(a['x']) < 5000
+  rows = (a['x'][:, 0] / bench.D).astype(int)
+  assert np.all(np.diff(rows) > 0)
+  assert np.array_equal(a['logp'], a['x'][:, 0] * 2.)
+  assert np.array_equal(a['accept'], rows % 2)
+  for k in shapes:
+    assert np.array_equal(a[k], np.load(str(tmp_path / 'b' / (k + '.npy'))))
 
 
 def test_bench_main_rejects_a_world_size_mismatch(tmp_path):
