@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PBH_ABI_VERSION 6
+#define PBH_ABI_VERSION 7
 #define PBH_MAX_DIM 32
 
 #define PBH_OK 0
@@ -44,8 +44,31 @@ enum pbh_target_kind {
   PBH_TARGET_GMM = 3,         /* logsumexp_k(logw_k + sum_i logpdf(x_i,mu_ki,sd_k)) */
   PBH_TARGET_NORM_PDF = 4,    /* prod_i norm.pdf(x_i, loc_i, scale_i)          */
   PBH_TARGET_UNIFORM_PDF = 5, /* prod_i uniform.pdf(x_i, lo_i, scale_i)        */
-  PBH_TARGET_MVN = 6          /* multivariate_normal.pdf at the permuted x     */
+  PBH_TARGET_MVN = 6,         /* multivariate_normal.pdf at the permuted x     */
+  PBH_TARGET_EXPR = 7         /* a scalar expression of x as a program the
+                                 kernels interpret (pbh_model.expr_*)          */
 };
+/* PBH_TARGET_EXPR: the program.  One instruction per code word, one result
+ * per instruction; the previous instruction's result is the accumulator, and
+ * an instruction with the store bit also writes its result to slot dst.
+ *   word = op | dst << 6 | store << 10 | akind << 11 | aidx << 13
+ *             | bkind << 21 | bidx << 23        (bit 31 clear)
+ * Operand kinds: 0 slot, 1 variable x[idx], 2 constant, 3 accumulator.  The
+ * density is the accumulator after the last instruction.  IEEE fp64; MAX /
+ * MIN propagate NaN as np.maximum / np.minimum do; POW is pow(a, b).       */
+enum pbh_expr_op {
+  PBH_EXPR_MOV = 0, PBH_EXPR_ADD = 1, PBH_EXPR_SUB = 2, PBH_EXPR_MUL = 3,
+  PBH_EXPR_DIV = 4, PBH_EXPR_NEG = 5, PBH_EXPR_ABS = 6, PBH_EXPR_SQRT = 7,
+  PBH_EXPR_EXP = 8, PBH_EXPR_LOG = 9, PBH_EXPR_LOG1P = 10, PBH_EXPR_EXPM1 = 11,
+  PBH_EXPR_MAX = 12, PBH_EXPR_MIN = 13, PBH_EXPR_POW = 14, PBH_EXPR_N_OPS = 15
+};
+enum pbh_expr_operand {
+  PBH_EXPR_SLOT = 0, PBH_EXPR_VAR = 1, PBH_EXPR_CONST = 2, PBH_EXPR_ACC = 3
+};
+#define PBH_EXPR_MAX_CODE 256
+#define PBH_EXPR_MAX_CONSTS 128
+#define PBH_EXPR_MAX_SLOTS 16
+#define PBH_EXPR_MAX_DIM 16
 enum pbh_pscale { PBH_PSCALE_LOG = 0, PBH_PSCALE_LIN = 1 };
 enum pbh_scores {
   PBH_SCORES_HASTINGS = 1, PBH_SCORES_METROPOLIS = 2, PBH_SCORES_GIBBS = 3
@@ -109,7 +132,8 @@ typedef struct pbh_model {
    *   UNIFORM_PDF: a = lo[d], b = scale[d]
    *   MVN        : a = mean[d], b = whitening U[d*d] row-major (scipy
    *                CovViaPSD._LP), c = {rank*log(2pi) + log_pdet}; the density
-   *                is taken at x[perm] with prob.py:354-357's fixed perm     */
+   *                is taken at x[perm] with prob.py:354-357's fixed perm
+   *   EXPR       : none of them; the expr_* fields at the end of the struct */
   const double *a, *b, *c, *e;
   const int32_t *perm;
   int64_t n;
@@ -128,6 +152,15 @@ typedef struct pbh_model {
   double tran_scale;    /* GAUSS_PDF: sigma                                   */
   const double *tran_offset;  /* GAUSS_PDF: loc offset per dim               */
   const int32_t *tran_order;  /* GAUSS_PDF: multiplication order of dims     */
+  /* PBH_TARGET_EXPR (dim <= PBH_EXPR_MAX_DIM): the program, checked by
+   * pbh_set_model before any launch -- every opcode, every variable /
+   * constant / slot index, that a slot or the accumulator is read only after
+   * it was written, and the limits above; PBH_ERR_ARG otherwise.            */
+  const int32_t *expr_code;   /* expr_n_code words, 1..PBH_EXPR_MAX_CODE      */
+  int32_t expr_n_code;
+  const double *expr_consts;  /* expr_n_consts values, 0..PBH_EXPR_MAX_CONSTS */
+  int32_t expr_n_consts;
+  int32_t expr_depth;         /* slots the program writes, 0..PBH_EXPR_MAX_SLOTS */
 } pbh_model;
 
 /* Proposal (replaces RF.set_delta / Field.eval_delta / apply_delta:
@@ -473,6 +506,12 @@ int pbh_check_normals(int device, int64_t n, const uint32_t *words,
 int pbh_check_normals64(int device, int64_t n, const uint32_t *words,
                         double *fast, double *ref);
 int pbh_bm64_tables(double *out);
+
+/* Evaluates a PBH_TARGET_EXPR program (checked as pbh_set_model checks it)
+ * at n points x[n][d] with the kernels' own device function; out[n].       */
+int pbh_eval_expr(int device, int32_t d, const int32_t *code, int32_t n_code,
+                  const double *consts, int32_t n_consts, int32_t depth,
+                  int64_t n, const double *x, double *out);
 
 #ifdef __cplusplus
 }

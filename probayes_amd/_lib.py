@@ -11,13 +11,13 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PBHIP_LIB', os.path.join(_HERE, 'libpbhip.so'))
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 DRAWS_GAUSS, DRAWS_LINREG = 0, 1   # enum pbh_draws
 MAX_DIM = 32
 
 # enums (pbhip.h)
 TARGET = {'diag_gauss': 1, 'norm_iid': 2, 'gmm': 3, 'norm_pdf': 4,
-          'uniform_pdf': 5, 'mvn': 6}
+          'uniform_pdf': 5, 'mvn': 6, 'expr': 7}
 PSCALE = {'log': 0, 'lin': 1}
 SCORES = {'hastings': 1, 'metropolis': 2, 'gibbs': 3}
 TRAN = {'const': 1, 'gauss_pdf': 2}
@@ -51,6 +51,9 @@ class PbhModel(ctypes.Structure):
       ('tran_kind', ctypes.c_int32), ('tran_sym', ctypes.c_int32),
       ('tran_value', ctypes.c_double), ('tran_scale', ctypes.c_double),
       ('tran_offset', _dp), ('tran_order', _ip),
+      ('expr_code', _ip), ('expr_n_code', ctypes.c_int32),
+      ('expr_consts', _dp), ('expr_n_consts', ctypes.c_int32),
+      ('expr_depth', ctypes.c_int32),
   ]
 
 
@@ -157,6 +160,9 @@ SIGNATURES = {
     'pbh_check_normals64': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _u32p,
                                            _dp, _dp]),
     'pbh_bm64_tables': (ctypes.c_int, [_dp]),
+    'pbh_eval_expr': (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, _ip,
+                                     ctypes.c_int32, _dp, ctypes.c_int32,
+                                     ctypes.c_int32, ctypes.c_int64, _dp, _dp]),
     'pbh_bool_perm_freq': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64,
                                           ctypes.c_int32,
                                           ctypes.POINTER(ctypes.c_uint8),

@@ -79,8 +79,8 @@ hipError_t launch_mh(const KArgs &a, hipStream_t s, size_t lds) {
     return launch_mh_d<D>(a, s, lds);
     PBH_DIMS(PBH_CASE)
 #undef PBH_CASE
-    default:
-      return hipErrorInvalidValue;
+    default:   // d = 13..15 exist for the expression target alone
+      return a.target == PBH_TARGET_EXPR ? launch_mh_expr(a, s) : hipErrorInvalidValue;
   }
 }
 

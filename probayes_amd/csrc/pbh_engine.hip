@@ -781,13 +781,64 @@ int pbh_cache_info(int64_t *idle_bytes, int64_t *hits, int64_t *misses) {
 // ---------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------
+// PBH_TARGET_EXPR: the program is checked here, on the host, so that the
+// interpreter may trust it (pbhip.h): every opcode, every operand's index
+// for its kind, a slot or the accumulator read only after it was written,
+// and the limits.  Returns nullptr, or what is wrong (pc: where).
+static const char *expr_check(int d, const int32_t *code, int32_t n_code,
+                              const double *consts, int32_t n_consts, int32_t depth,
+                              int *pc_out) {
+  *pc_out = -1;
+  if (d < 1 || d > PBH_EXPR_MAX_DIM) return "dim outside 1..16";
+  if (!code || n_code < 1 || n_code > PBH_EXPR_MAX_CODE) return "code words outside 1..256";
+  if (n_consts < 0 || n_consts > PBH_EXPR_MAX_CONSTS || (n_consts && !consts))
+    return "constants outside 0..128 (or missing)";
+  if (depth < 0 || depth > PBH_EXPR_MAX_SLOTS) return "depth outside 0..16";
+  uint32_t written = 0;
+  for (int pc = 0; pc < n_code; ++pc) {
+    *pc_out = pc;
+    if (code[pc] < 0) return "code word with bit 31 set";
+    const uint32_t w = (uint32_t)code[pc], op = w & 63u;
+    if (op >= PBH_EXPR_N_OPS) return "unknown opcode";
+    const bool binary = (op >= PBH_EXPR_ADD && op <= PBH_EXPR_DIV) || op >= PBH_EXPR_MAX;
+    for (int j = 0; j < (binary ? 2 : 1); ++j) {
+      const uint32_t kind = (w >> (j ? 21 : 11)) & 3u, idx = (w >> (j ? 23 : 13)) & 255u;
+      if (kind == PBH_EXPR_SLOT && !(idx < (uint32_t)depth && ((written >> idx) & 1u)))
+        return "slot read before it is written (or outside the depth)";
+      if (kind == PBH_EXPR_VAR && idx >= (uint32_t)d) return "variable index outside the dims";
+      if (kind == PBH_EXPR_CONST && idx >= (uint32_t)n_consts) return "constant index out of range";
+      if (kind == PBH_EXPR_ACC && pc == 0) return "accumulator read by the first instruction";
+    }
+    if ((w >> 10) & 1u) {
+      const uint32_t dst = (w >> 6) & 15u;
+      if (dst >= (uint32_t)depth) return "stored slot outside the depth";
+      written |= 1u << dst;
+    }
+  }
+  return nullptr;
+}
+
+// the program into a block of doubles: 256 constants (padded with zeros),
+// then 256 code words (padded with MOV words); returns the constants' offset
+static size_t expr_pack(std::vector<double> &blk, const int32_t *code, int32_t n_code,
+                        const double *consts, int32_t n_consts) {
+  const size_t o = blk.size();
+  blk.resize(o + 256 + PBH_EXPR_MAX_CODE / 2, 0.0);
+  for (int i = 0; i < n_consts; ++i) blk[o + i] = consts[i];
+  std::memcpy(&blk[o + 256], code, (size_t)n_code * sizeof(int32_t));
+  return o;
+}
+
 int pbh_set_model(pbh_engine *e, const pbh_model *m) {
   if (check_ptr(e, "engine") || check_ptr(m, "model")) return PBH_ERR_ARG;
   SRV_STOP(e);
   const int d = m->dim;
   if (d < 1 || d > PBH_MAX_DIM)
     return fail(PBH_ERR_ARG, "dim %d outside 1..%d", d, PBH_MAX_DIM);
-  if (!pbh::mh_dim_supported(d))
+  const bool is_expr = m->target_kind == PBH_TARGET_EXPR;
+  if (is_expr && m->scores == PBH_SCORES_GIBBS)
+    return fail(PBH_ERR_UNSUPPORTED, "an expression target has no Gibbs form");
+  if (!(is_expr ? d <= PBH_EXPR_MAX_DIM : pbh::mh_dim_supported(d)))
     return fail(PBH_ERR_UNSUPPORTED,
                 "dim %d has no compiled kernel (1-12, 16, 20, 24, 32)", d);
   if (m->pscale != PBH_PSCALE_LOG && m->pscale != PBH_PSCALE_LIN)
@@ -816,6 +867,13 @@ int pbh_set_model(pbh_engine *e, const pbh_model *m) {
     case PBH_TARGET_NORM_PDF:
     case PBH_TARGET_UNIFORM_PDF: na = nb = d; break;
     case PBH_TARGET_MVN: na = d; nb = (int64_t)d * d; nc = 1; break;
+    case PBH_TARGET_EXPR: {
+      int pc = -1;
+      if (const char *why = expr_check(d, m->expr_code, m->expr_n_code, m->expr_consts,
+                                       m->expr_n_consts, m->expr_depth, &pc))
+        return fail(PBH_ERR_ARG, "expression program: %s (code word %d)", why, pc);
+      break;
+    }
     default: return fail(PBH_ERR_ARG, "bad target kind %d", m->target_kind);
   }
   if ((na && !A) || (nb && !B) || (nc && !C) || (ne && !E))
@@ -859,6 +917,9 @@ int pbh_set_model(pbh_engine *e, const pbh_model *m) {
     const double st[2] = {mean, s2};
     ow = pack(blk, st, 2);
   }
+  size_t oexpr = 0;
+  if (is_expr)
+    oexpr = expr_pack(blk, m->expr_code, m->expr_n_code, m->expr_consts, m->expr_n_consts);
   uint32_t lo_incl = 0, hi_incl = 0, ufun = 0;
   if (m->has_prior) {
     if (!m->prior_lo || !m->prior_hi || !m->prior_lo_incl || !m->prior_hi_incl)
@@ -900,6 +961,9 @@ int pbh_set_model(pbh_engine *e, const pbh_model *m) {
   k.d = d; k.target = m->target_kind; k.pscale = m->pscale; k.scores = m->scores;
   k.ta = base + oa; k.tb = base + ob; k.tc = base + oc; k.te = base + oe;
   k.tw = base + ow; k.ksum = ksum;
+  k.econst = is_expr ? base + oexpr : nullptr;
+  k.ecode = is_expr ? reinterpret_cast<const int32_t *>(base + oexpr + 256) : nullptr;
+  k.en = is_expr ? m->expr_n_code : 0;
   k.tn = (m->target_kind == PBH_TARGET_NORM_IID || m->target_kind == PBH_TARGET_GMM) ? m->n : 0;
   k.i0 = m->i0; k.i1 = m->i1;
   k.has_prior = m->has_prior ? 1 : 0;
@@ -1773,7 +1837,9 @@ int pbh_legacy_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
   la.lgtab = e->lgtab;
   bool ident = true;
   for (int j = 0; j < (int)e->draw_order.size(); ++j) ident = ident && e->draw_order[j] == j;
-  const bool fused = e->legacy_fused && ident &&
+  // the fused kernel has no instance for the expression target (its generic
+  // form's density switch would return NaN): generation, then run
+  const bool fused = e->legacy_fused && ident && e->k.target != PBH_TARGET_EXPR &&
                      pbh::launch_legacy_mh(la, k, e->stream, true) == hipSuccess;
   // the thresholds (pbh_set_record_threshold): MH only (Gibbs draws none)
   const bool keep_thr = e->rec_thr && !e->has_gibbs;
@@ -2639,6 +2705,47 @@ int pbh_check_accept(int device, int64_t n, const double *lp,
   if (rc) return rc;
   if (err != hipSuccess)
     return fail(PBH_ERR_HIP, "pbh_check_accept: %s", hipGetErrorString(err));
+  return PBH_OK;
+}
+
+int pbh_eval_expr(int device, int32_t d, const int32_t *code, int32_t n_code,
+                  const double *consts, int32_t n_consts, int32_t depth, int64_t n,
+                  const double *x, double *out) {
+  if (check_ptr(x, "x") || check_ptr(out, "out")) return PBH_ERR_ARG;
+  if (n <= 0) return fail(PBH_ERR_ARG, "n must be positive");
+  int pc = -1;
+  if (const char *why = expr_check(d, code, n_code, consts, n_consts, depth, &pc))
+    return fail(PBH_ERR_ARG, "expression program: %s (code word %d)", why, pc);
+  HIP_TRY(hipSetDevice(device));
+  std::vector<double> blk;
+  expr_pack(blk, code, n_code, consts, n_consts);
+  std::vector<double> xt((size_t)d * n);   // [n][d] -> [d][n]
+  for (int64_t i = 0; i < n; ++i)
+    for (int k = 0; k < d; ++k) xt[(size_t)k * n + i] = x[(size_t)i * d + k];
+  double *dblk = nullptr, *dx = nullptr, *dout = nullptr;
+  int rc = dalloc(dblk, blk.size());
+  if (!rc) rc = dalloc(dx, xt.size());
+  if (!rc) rc = dalloc(dout, n);
+  hipError_t err = hipSuccess;
+  if (!rc) {
+    err = hipMemcpy(dblk, blk.data(), blk.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (err == hipSuccess)
+      err = hipMemcpy(dx, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+      KArgs k{};
+      k.d = d;
+      k.target = PBH_TARGET_EXPR;
+      k.econst = dblk;
+      k.ecode = reinterpret_cast<const int32_t *>(dblk + 256);
+      k.en = n_code;
+      err = pbh::launch_eval_expr(k, n, dx, dout);
+    }
+    if (err == hipSuccess) err = hipMemcpy(out, dout, n * sizeof(double), hipMemcpyDeviceToHost);
+  }
+  dfree(dblk); dfree(dx); dfree(dout);
+  if (rc) return rc;
+  if (err != hipSuccess)
+    return fail(PBH_ERR_HIP, "pbh_eval_expr: %s", hipGetErrorString(err));
   return PBH_OK;
 }
 

@@ -148,6 +148,10 @@ struct KArgs {
   int64_t *nacc;
   // ---- production fp64 normals: bm64 tables (pbh_device.h), global copy
   const double *bm64;
+  // ---- PBH_TARGET_EXPR: the program (checked by the host, pbhip.h) ----
+  const int32_t *ecode;   // en code words
+  const double *econst;   // constants
+  int32_t en;
 };
 // The resident server's host command block and completion words (engine:
 // pbh_server_*, kernel: mh_pair_kernel<..., SRV>).  The host writes the
@@ -194,6 +198,10 @@ hipError_t launch_mh_server(const KArgs &a, hipStream_t s, int32_t *wgs, bool ch
 hipError_t launch_xo_seed(uint32_t *xo, int64_t n, int64_t off, uint64_t seed,
                           hipStream_t s);
 bool mh_dim_supported(int d);
+// PBH_TARGET_EXPR: mh_kernel<D, RNG, PBH_TARGET_EXPR, 0>, d = 1..16
+// (pbh_expr.hip); launch_eval_expr evaluates the program at x [d][n]
+hipError_t launch_mh_expr(const KArgs &a, hipStream_t s);
+hipError_t launch_eval_expr(const KArgs &a, int64_t n, const double *x, double *out);
 hipError_t launch_check_normals(int64_t n, const uint32_t *words, double *fast,
                                 double *ref);
 // bm96_pair (the production fp64 normals) and its libm form on n word triples.

@@ -69,6 +69,19 @@ def mvn_psd(mean, cov):
   return _f64(co._LP), float(const)
 
 
+def eval_expr(code, consts, depth, x, device=0):
+  """pbh_eval_expr: the expr program at the points x [n, d] with the
+  kernels' own device function (diagnostic; probayes_amd.expr.evaluate is
+  the NumPy definition)."""
+  x = np.ascontiguousarray(np.atleast_2d(x), np.float64)
+  n, d = x.shape
+  code, consts = _i32(code).reshape(-1), _f64(consts).reshape(-1)
+  out = np.empty(n)
+  _lib.call('pbh_eval_expr', int(device), d, _ip(code), len(code), _dp(consts),
+            len(consts), int(depth), n, _dp(x), _dp(out))
+  return out
+
+
 def unpack_stats(out, counts, d):
   """[world][3d+1][n_max] gather block (pbh_rccl_allgather_stats) -> the
   per-chain statistics of all ranks concatenated in rank (= global chain)
@@ -169,6 +182,12 @@ class Engine:
       U, const = mvn_psd(tg['mean'], tg['cov'])
       m.a, m.b = _dp(arr(tg['mean'])), _dp(arr(U))
       m.c = _dp(arr(np.array([const])))
+    elif kind == 'expr':
+      m.expr_code = _ip(arr(tg['code'], _i32))
+      m.expr_n_code = len(tg['code'])
+      m.expr_consts = _dp(arr(tg['consts']))
+      m.expr_n_consts = len(tg['consts'])
+      m.expr_depth = tg['depth']
     pr = s['prior']
     if pr is not None:
       m.has_prior = 1

@@ -20,6 +20,9 @@ Recognised forms
          components), then m = np.max(a); m + np.log(np.sum(np.exp(a - m)))
          or scipy.special.logsumexp(a)                          -> gmm
          (traced through NumPy's __array_ufunc__ / __array_function__)
+         any other scalar expression of the variables in + - * / ** abs,
+         exp log sqrt log1p expm1 square maximum minimum and
+         norm.logpdf / norm.pdf (probayes_amd/expr.py)           -> expr
   plus the scipy objects themselves (norm.pdf/logpdf, uniform.pdf,
   multivariate_normal) and the descriptor callables of probayes_amd.models.
 """
@@ -401,6 +404,14 @@ def trace_logsumexp(fn, keys):
       raise NotLowerable('mixture sds must be shared across variables')
     sd = np.array(s)
   return {'kind': 'gmm', 'logw': logw, 'mu': mu, 'sd': sd}, 'log'
+
+
+def trace_expr(fn, keys):
+  """Any scalar density built from the operations probayes_amd.expr lists ->
+  the expr target (a program the kernels interpret), or NotLowerable.  Tried
+  last: a callable that matches a closed form lowers to that form."""
+  from probayes_amd import expr
+  return expr.trace_expr(fn, keys)
 
 
 def is_same_callable(a, b):

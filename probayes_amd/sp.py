@@ -261,7 +261,12 @@ class SP:
         try:
           target, ps = L.trace_logsumexp(prob, names)
         except L.NotLowerable:
-          raise e
+          # no closed form: the general scalar expression (expr.py), in the
+          # declared pscale like every callable of the reference (rf.py:91)
+          try:
+            return L.trace_expr(prob, names), self._pscale(pscale_kw)
+          except L.NotLowerable as ex:
+            raise ex from e
       return target, (self._pscale(pscale_kw) if pscale_kw else ps)
     raise L.NotLowerable('density {} is not a recognised form'.format(prob))
 

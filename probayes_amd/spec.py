@@ -11,6 +11,9 @@ encodes the closed set of model forms the engine lowers:
                 norm_pdf    prod_i norm.pdf(x_i, loc_i, scale_i)  (lin)
                 uniform_pdf prod_i uniform.pdf(x_i, lo_i, scale_i) (lin)
                 mvn         multivariate_normal.pdf at the permuted vector (lin)
+                expr        any scalar expression of the variables, as a program
+                            {code, consts, depth} the kernels interpret
+                            (probayes_amd/expr.py; pscale as declared)
   prior         joint=True uniform prior of the root RVs (rv_utils.py:8-47)
   ufun          per-dim 1 = (log, exp) change of variable (variable.py:693-697)
   proposal kind gauss   callable Delta(norm.rvs(loc, scale)) per dim
@@ -29,7 +32,8 @@ encodes the closed set of model forms the engine lowers:
 """
 import numpy as np
 
-TARGETS = ('diag_gauss', 'norm_iid', 'gmm', 'norm_pdf', 'uniform_pdf', 'mvn')
+TARGETS = ('diag_gauss', 'norm_iid', 'gmm', 'norm_pdf', 'uniform_pdf', 'mvn',
+           'expr')
 PROPOSALS = ('gauss', 'sphere', 'uniform', 'gibbs', 'vardelta')
 SCORES = ('hastings', 'metropolis', 'gibbs')
 
@@ -85,6 +89,12 @@ def make_spec(dim, target, proposal, scores='hastings', pscale=None,
   elif kind == 'mvn':
     target['mean'] = _vec(target['mean'], d, 'mean')
     target['cov'] = np.asarray(target['cov'], dtype=np.float64).reshape(d, d)
+  elif kind == 'expr':
+    from probayes_amd import expr
+    target['code'] = np.asarray(target['code'], dtype=np.int32).reshape(-1)
+    target['consts'] = np.asarray(target['consts'], dtype=np.float64).reshape(-1)
+    target['depth'] = int(target['depth'])
+    expr.check_program(target['code'], target['consts'], target['depth'], d)
   if prior is not None:
     prior = dict(prior)
     prior['lo'] = _vec(prior['lo'], d, 'prior.lo')
