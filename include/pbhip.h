@@ -28,6 +28,10 @@ extern "C" {
 #endif
 
 #define PBH_ABI_VERSION 7
+/* Additions that leave every version-7 call and struct prefix as it was bump
+ * the revision: 1 = pbh_model.expr_data / expr_n_obs / expr_n_cols (a caller
+ * passes the whole struct, zero-initialised), pbh_eval_expr_data.            */
+#define PBH_ABI_REVISION 1
 #define PBH_MAX_DIM 32
 
 #define PBH_OK 0
@@ -56,11 +60,25 @@ enum pbh_target_kind {
  * Operand kinds: 0 slot, 1 variable x[idx], 2 constant, 3 accumulator.  The
  * density is the accumulator after the last instruction.  IEEE fp64; MAX /
  * MIN propagate NaN as np.maximum / np.minimum do; POW is pow(a, b).       */
+/* Loop regions (a program with data, pbh_model.expr_data): all data columns
+ * have one length n; a value that depends on one is summed over the n
+ * observations by a non-nested region
+ *   LOOP | len << 13,  len body words,  SUM | dst << 6 | store << 10 | 3 << 11
+ * whose body runs once per observation j with an accumulator of its own, and
+ * whose SUM word leaves the sum of the body's last value over j in the
+ * accumulator (and in slot dst).  In a body a variable index >= 16 is data
+ * column idx - 16 at observation j, a slot index >= 16 is body temporary
+ * idx - 16 (PBH_EXPR_MAX_TEMPS of them), a slot index < 16 reads an outer
+ * slot, and the store field names a body temporary.  The sum is NumPy's 1-D
+ * pairwise sum in every RNG mode: sequential below 8 terms, eight
+ * accumulators per block up to 128, halving (to a multiple of 8) above.      */
 enum pbh_expr_op {
   PBH_EXPR_MOV = 0, PBH_EXPR_ADD = 1, PBH_EXPR_SUB = 2, PBH_EXPR_MUL = 3,
   PBH_EXPR_DIV = 4, PBH_EXPR_NEG = 5, PBH_EXPR_ABS = 6, PBH_EXPR_SQRT = 7,
   PBH_EXPR_EXP = 8, PBH_EXPR_LOG = 9, PBH_EXPR_LOG1P = 10, PBH_EXPR_EXPM1 = 11,
-  PBH_EXPR_MAX = 12, PBH_EXPR_MIN = 13, PBH_EXPR_POW = 14, PBH_EXPR_N_OPS = 15
+  PBH_EXPR_MAX = 12, PBH_EXPR_MIN = 13, PBH_EXPR_POW = 14, PBH_EXPR_N_OPS = 15,
+  /* region markers, outside the elementwise opcodes 0..N_OPS-1 */
+  PBH_EXPR_LOOP = 32, PBH_EXPR_SUM = 33
 };
 enum pbh_expr_operand {
   PBH_EXPR_SLOT = 0, PBH_EXPR_VAR = 1, PBH_EXPR_CONST = 2, PBH_EXPR_ACC = 3
@@ -69,6 +87,10 @@ enum pbh_expr_operand {
 #define PBH_EXPR_MAX_CONSTS 128
 #define PBH_EXPR_MAX_SLOTS 16
 #define PBH_EXPR_MAX_DIM 16
+#define PBH_EXPR_BODY_BASE 16   /* body: data column / temporary indices from here */
+#define PBH_EXPR_MAX_COLS 8
+#define PBH_EXPR_MAX_TEMPS 4
+#define PBH_EXPR_MAX_OBS 65536
 enum pbh_pscale { PBH_PSCALE_LOG = 0, PBH_PSCALE_LIN = 1 };
 enum pbh_scores {
   PBH_SCORES_HASTINGS = 1, PBH_SCORES_METROPOLIS = 2, PBH_SCORES_GIBBS = 3
@@ -161,6 +183,15 @@ typedef struct pbh_model {
   const double *expr_consts;  /* expr_n_consts values, 0..PBH_EXPR_MAX_CONSTS */
   int32_t expr_n_consts;
   int32_t expr_depth;         /* slots the program writes, 0..PBH_EXPR_MAX_SLOTS */
+  /* a program with loop regions: expr_data[expr_n_cols][expr_n_obs], copied
+   * to the device with the program (NULL / 0 / 0: a program without regions).
+   * Checked with the program: region bounds, no nesting, column and temporary
+   * indices, a temporary read only after the body wrote it, the accumulator
+   * not read by a body's first word, no outer slot written inside a body,
+   * 1 <= expr_n_cols <= PBH_EXPR_MAX_COLS, 1 <= expr_n_obs <= PBH_EXPR_MAX_OBS. */
+  const double *expr_data;
+  int32_t expr_n_obs;
+  int32_t expr_n_cols;
 } pbh_model;
 
 /* Proposal (replaces RF.set_delta / Field.eval_delta / apply_delta:
@@ -210,6 +241,7 @@ typedef struct pbh_engine pbh_engine;
 /* ---- engine lifetime ---------------------------------------------------- */
 const char *pbh_last_error(void);
 int pbh_abi_version(void);
+int pbh_abi_revision(void);   /* PBH_ABI_REVISION */
 int pbh_device_count(int *count);
 int pbh_create(int device, pbh_engine **out);
 /* Destroys the engine.  Its device buffers, stream and events (drained) stay
@@ -512,6 +544,13 @@ int pbh_bm64_tables(double *out);
 int pbh_eval_expr(int device, int32_t d, const int32_t *code, int32_t n_code,
                   const double *consts, int32_t n_consts, int32_t depth,
                   int64_t n, const double *x, double *out);
+/* The same for a program with loop regions over data[n_cols][n_obs], through
+ * the interpreter of the data kernels.  PBH_EXPR_DATA_WIDE=0 in the
+ * environment selects the one-observation-at-a-time body (same bits).       */
+int pbh_eval_expr_data(int device, int32_t d, const int32_t *code, int32_t n_code,
+                       const double *consts, int32_t n_consts, int32_t depth,
+                       const double *data, int32_t n_cols, int32_t n_obs,
+                       int64_t n, const double *x, double *out);
 
 #ifdef __cplusplus
 }

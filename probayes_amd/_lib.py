@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PBHIP_LIB', os.path.join(_HERE, 'libpbhip.so'))
 
 ABI_VERSION = 7
+ABI_REVISION = 1   # PBH_ABI_REVISION: additions within version 7
 DRAWS_GAUSS, DRAWS_LINREG = 0, 1   # enum pbh_draws
 MAX_DIM = 32
 
@@ -54,6 +55,8 @@ class PbhModel(ctypes.Structure):
       ('expr_code', _ip), ('expr_n_code', ctypes.c_int32),
       ('expr_consts', _dp), ('expr_n_consts', ctypes.c_int32),
       ('expr_depth', ctypes.c_int32),
+      ('expr_data', _dp), ('expr_n_obs', ctypes.c_int32),
+      ('expr_n_cols', ctypes.c_int32),
   ]
 
 
@@ -76,6 +79,7 @@ class PbhGibbs(ctypes.Structure):
 SIGNATURES = {
     'pbh_last_error': (ctypes.c_char_p, []),
     'pbh_abi_version': (ctypes.c_int, []),
+    'pbh_abi_revision': (ctypes.c_int, []),
     'pbh_device_count': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
     'pbh_create': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     'pbh_destroy': (ctypes.c_int, [ctypes.c_void_p]),
@@ -163,6 +167,11 @@ SIGNATURES = {
     'pbh_eval_expr': (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, _ip,
                                      ctypes.c_int32, _dp, ctypes.c_int32,
                                      ctypes.c_int32, ctypes.c_int64, _dp, _dp]),
+    'pbh_eval_expr_data': (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, _ip,
+                                          ctypes.c_int32, _dp, ctypes.c_int32,
+                                          ctypes.c_int32, _dp, ctypes.c_int32,
+                                          ctypes.c_int32, ctypes.c_int64, _dp,
+                                          _dp]),
     'pbh_bool_perm_freq': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64,
                                           ctypes.c_int32,
                                           ctypes.POINTER(ctypes.c_uint8),
@@ -204,6 +213,9 @@ def load():
   if lib.pbh_abi_version() != ABI_VERSION:
     raise OSError('libpbhip ABI {} != {}'.format(lib.pbh_abi_version(),
                                                   ABI_VERSION))
+  if lib.pbh_abi_revision() != ABI_REVISION:
+    raise OSError('libpbhip ABI revision {} != {}'.format(lib.pbh_abi_revision(),
+                                                           ABI_REVISION))
   _LIB = lib
   return lib
 

@@ -80,7 +80,8 @@ hipError_t launch_mh(const KArgs &a, hipStream_t s, size_t lds) {
     PBH_DIMS(PBH_CASE)
 #undef PBH_CASE
     default:   // d = 13..15 exist for the expression target alone
-      return a.target == PBH_TARGET_EXPR ? launch_mh_expr(a, s) : hipErrorInvalidValue;
+      if (a.target != PBH_TARGET_EXPR) return hipErrorInvalidValue;
+      return a.edata ? launch_mh_expr_data(a, s) : launch_mh_expr(a, s);
   }
 }
 

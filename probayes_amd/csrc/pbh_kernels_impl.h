@@ -196,6 +196,9 @@ __device__ __forceinline__ double gmm_fast(const KArgs &a, const double (&x)[D])
 // PBH_TARGET_EXPR: the density is a program (expr_density below)
 template <int D>
 __device__ __forceinline__ double expr_density(const KArgs &a, const double (&x)[D]);
+// ... with loop regions over data (defined in pbh_expr_data.hip alone)
+template <int D>
+__device__ __forceinline__ double expr_data_density(const KArgs &a, const double (&x)[D]);
 
 // lx (production, may be null): log of x for the dims with the (log, exp)
 // ufun, as the proposal formed them (x' = exp(log x + delta)), so the
@@ -332,6 +335,10 @@ __device__ __forceinline__ double joint_density(const KArgs &a,
       // only in the kernels compiled for it (mh_kernel<D, RNG, EXPR, 0>,
       // which launch_mh_d always takes for this target)
       if constexpr (TGT == PBH_TARGET_EXPR) out = expr_density<D>(a, x);
+      else out = __builtin_nan("");
+      break;
+    case kTargetExprData:   // never a.target: mh_kernel<D, RNG, kTargetExprData, 0>
+      if constexpr (TGT == kTargetExprData) out = expr_data_density<D>(a, x);
       else out = __builtin_nan("");
       break;
     default:
@@ -3660,7 +3667,9 @@ hipError_t launch_mh_d(const KArgs &a, hipStream_t st, size_t lds) {
   if (a.rng == PBH_RNG_PHILOX_FP32) return hipErrorInvalidValue;   // pair kernel only
   // the expression target: its own instances (pbh_expr.hip), never the
   // generic form below, whose density switch does not hold the interpreter
-  if (a.target == PBH_TARGET_EXPR) return launch_mh_expr(a, st);
+  // (a program with loop regions: the kernels of pbh_expr_data.hip)
+  if (a.target == PBH_TARGET_EXPR)
+    return a.edata ? launch_mh_expr_data(a, st) : launch_mh_expr(a, st);
   // Specialised forms: the cfg2 diagonal Gaussian with the callable Gaussian
   // delta at every d; the other example forms at the small d they use.
   if (a.target == PBH_TARGET_DIAG_GAUSS && a.prop == PBH_PROP_GAUSS) {

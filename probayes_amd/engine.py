@@ -69,14 +69,21 @@ def mvn_psd(mean, cov):
   return _f64(co._LP), float(const)
 
 
-def eval_expr(code, consts, depth, x, device=0):
+def eval_expr(code, consts, depth, x, device=0, data=None):
   """pbh_eval_expr: the expr program at the points x [n, d] with the
   kernels' own device function (diagnostic; probayes_amd.expr.evaluate is
-  the NumPy definition)."""
+  the NumPy definition).  data [C, n_obs]: a program with loop regions, through
+  pbh_eval_expr_data (the interpreter of the data kernels)."""
   x = np.ascontiguousarray(np.atleast_2d(x), np.float64)
   n, d = x.shape
   code, consts = _i32(code).reshape(-1), _f64(consts).reshape(-1)
   out = np.empty(n)
+  if data is not None:
+    data = np.ascontiguousarray(np.atleast_2d(_f64(data)))
+    _lib.call('pbh_eval_expr_data', int(device), d, _ip(code), len(code),
+              _dp(consts), len(consts), int(depth), _dp(data), data.shape[0],
+              data.shape[1], n, _dp(x), _dp(out))
+    return out
   _lib.call('pbh_eval_expr', int(device), d, _ip(code), len(code), _dp(consts),
             len(consts), int(depth), n, _dp(x), _dp(out))
   return out
@@ -188,6 +195,9 @@ class Engine:
       m.expr_consts = _dp(arr(tg['consts']))
       m.expr_n_consts = len(tg['consts'])
       m.expr_depth = tg['depth']
+      if tg.get('data') is not None:     # [C, n]: the loop regions' columns
+        m.expr_data = _dp(arr(tg['data']))
+        m.expr_n_cols, m.expr_n_obs = tg['data'].shape
     pr = s['prior']
     if pr is not None:
       m.has_prior = 1

@@ -1,9 +1,10 @@
 """Expression target: a scalar density as a small program (data, not code).
 
 A density callable that matches none of the closed forms is traced once with
-symbolic scalars (trace_expr) and compiled to a straight-line program that the
-HIP kernels interpret (pbh_kernels_impl.h expr_density): the same program for
-every chain, so its control flow is wave-uniform.
+symbolic scalars (trace_expr; the 1-D arrays it holds become data columns) and
+compiled to a straight-line program that the HIP kernels interpret
+(pbh_kernels_impl.h expr_density, pbh_expr_data.hip expr_data_density): the
+same program for every chain, so its control flow is wave-uniform.
 
 The machine
   One instruction per code word, one result per instruction.  The result of
@@ -19,6 +20,26 @@ The machine
   Limits: MAX_CODE words, MAX_CONSTS constants, MAX_SLOTS slots, MAX_DIM
   variables.  A slot is read only after it was written, the accumulator only
   after the first instruction (pbh_set_model checks every program).
+
+Loop regions (likelihoods summed over observed data)
+  A density may hold 1-D data arrays, all of one length n.  A value that
+  depends on one is a vector; a program reduces it to a scalar in a non-nested
+  loop region:
+
+    LOOP | body_len << 13      opens the region
+    body_len body words        a straight-line program run once per observation
+                               j = 0..n-1, with an accumulator of its own
+    SUM  | dst << 6 | store << 10 | ACC << 11
+                               closes it: the accumulator becomes the sum over
+                               j of the body's last value (and goes to slot dst)
+
+  Inside a body a VAR index >= 16 is data column idx - 16 at observation j, a
+  SLOT index >= 16 is body temporary idx - 16 (MAX_TEMPS of them), a SLOT
+  index < 16 reads an outer slot, and the store field names a body temporary.
+  The sum is NumPy's 1-D pairwise sum (sequential below 8 terms, eight
+  accumulators per block up to 128, halving above that).  Limits: MAX_COLS
+  columns, 1 <= n <= MAX_OBS.  LOOP and SUM lie outside range(N_OPS): a
+  program without data holds neither.
 
 evaluate() below is the written definition of each opcode: a plain NumPy
 interpreter, vectorised over chains, whose loops are the ones the callable
@@ -38,6 +59,11 @@ OP_NAMES = ('mov', 'add', 'sub', 'mul', 'div', 'neg', 'abs', 'sqrt', 'exp',
             'log', 'log1p', 'expm1', 'max', 'min', 'pow')
 ARITY = (1, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2)
 SLOT, VAR, CONST, ACC = range(4)
+# loop regions: outside range(N_OPS), so that a program without data arrays
+# keeps its words
+LOOP, SUM = 32, 33
+MAX_COLS, MAX_TEMPS, MAX_OBS = 8, 4, 65536
+BODY_BASE = 16   # a body's VAR / SLOT index from here on: data column / temporary
 
 
 def _not_lowerable(msg):
@@ -67,14 +93,32 @@ _BINARY = {ADD: np.add, SUB: np.subtract, MUL: np.multiply,
            DIV: np.true_divide, MAX: np.maximum, MIN: np.minimum}
 
 
-def evaluate(code, consts, x):
+def _apply(op, va, fetch_b):
+  if op == MOV:
+    return va
+  if op in _UNARY:
+    return _UNARY[op](va)
+  if op == POW:
+    vb = fetch_b()
+    return va ** (float(vb) if np.ndim(vb) == 0 else vb)
+  return _BINARY[op](va, fetch_b())
+
+
+def evaluate(code, consts, x, data=None):
   """The program at the points x [n, d] (or [d]) -> values [n] (or a scalar).
-  IEEE float64 throughout; POW is NumPy's `a ** c`."""
+  IEEE float64 throughout; POW is NumPy's `a ** c`.  data [C, n_obs]: the
+  columns the loop regions read.  A region's terms are laid out [points,
+  n_obs], C-contiguous, and reduced along the last axis: NumPy's pairwise sum
+  of each point's terms (a reduction along axis 0 would add rows in
+  sequence)."""
   x = np.asarray(x, np.float64)
   single = x.ndim == 1
   x = np.ascontiguousarray(np.atleast_2d(x).T)   # [d, n]: contiguous columns
   n = x.shape[1]
   consts = np.asarray(consts, np.float64)
+  if data is not None:
+    data = np.ascontiguousarray(np.atleast_2d(np.asarray(data, np.float64)))
+  code = [int(w) for w in np.asarray(code).reshape(-1)]
   slots = {}
   acc = None
 
@@ -88,22 +132,46 @@ def evaluate(code, consts, x):
       return consts[i]          # a float64 scalar, as in the callable
     return acc
 
-  with np.errstate(all='ignore'):
-    for w in np.asarray(code).reshape(-1):
+  def region(body):
+    """sum over the observations of the body's last value -> [n]"""
+    n_obs = data.shape[1]
+    temps = {}
+    bacc = None
+
+    def bfetch(o):
+      kind, i = o
+      if kind == SLOT:
+        return temps[i - BODY_BASE] if i >= BODY_BASE else slots[i][:, None]
+      if kind == VAR:
+        return data[i - BODY_BASE][None, :] if i >= BODY_BASE else x[i][:, None]
+      if kind == CONST:
+        return consts[i]
+      return bacc
+
+    for w in body:
       op, dst, store, a, b = decode(w)
-      va = fetch(a)
-      if op == MOV:
-        r = va
-      elif op in _UNARY:
-        r = _UNARY[op](va)
-      elif op == POW:
-        vb = fetch(b)
-        r = va ** (float(vb) if np.ndim(vb) == 0 else vb)
+      r = _apply(op, bfetch(a), lambda: bfetch(b))
+      bacc = np.asarray(r, np.float64)
+      if store:
+        temps[dst] = bacc
+    terms = np.ascontiguousarray(np.broadcast_to(bacc, (n, n_obs)))
+    return np.add.reduce(terms, axis=1)
+
+  with np.errstate(all='ignore'):
+    pc = 0
+    while pc < len(code):
+      op, dst, store, a, b = decode(code[pc])
+      if op == LOOP:
+        length = a[1]
+        r = region(code[pc + 1:pc + 1 + length])
+        pc += length + 1          # at the SUM word, which may store the sum
+        op, dst, store, a, b = decode(code[pc])
       else:
-        r = _BINARY[op](va, fetch(b))
+        r = _apply(op, fetch(a), lambda: fetch(b))
       acc = np.broadcast_to(np.asarray(r, np.float64), (n,))
       if store:
         slots[dst] = acc
+      pc += 1
   out = np.array(acc)
   return out[0] if single else out
 
@@ -127,6 +195,14 @@ def _operand(v, what):
     return v
   c = _const(v)
   if c is None:
+    if isinstance(v, np.ndarray) and v.dtype.kind in 'fiub':
+      if v.ndim != 1:
+        raise _not_lowerable('{}-D array in a density ({}): data arrays are 1-D'
+                             .format(v.ndim, what))
+      if not 1 <= v.size <= MAX_OBS:
+        raise _not_lowerable('data array of {} observations outside 1..{} ({})'
+                             .format(v.size, MAX_OBS, what))
+      return Val(None, col=np.ascontiguousarray(v, np.float64), n=v.size)
     if isinstance(v, (np.ndarray, list, tuple)):
       raise _not_lowerable('array-valued constant in a scalar density ({})'
                            .format(what))
@@ -135,9 +211,41 @@ def _operand(v, what):
   return c
 
 
+def _symbolic(v):
+  """Depends on a variable (a data column alone does not)."""
+  return isinstance(v, Val) and v.col is None
+
+
 def _mk(op, a, b=None):
-  return Val(op, _operand(a, OP_NAMES[op]),
-             None if b is None else _operand(b, OP_NAMES[op]))
+  ops = [_operand(v, OP_NAMES[op]) for v in ((a,) if b is None else (a, b))]
+  lens = {v.n for v in ops if isinstance(v, Val) and v.n}
+  if len(lens) > 1:
+    raise _not_lowerable('data arrays of two lengths ({}) in one density'
+                         .format(' and '.join(str(n) for n in sorted(lens))))
+  if op == LOG and isinstance(ops[0], Val) and ops[0].op == SUM and ops[0].a.op == EXP:
+    # as before this target had sums: a mixture is the gmm form or nothing
+    raise _not_lowerable('np.log(np.sum(np.exp(v))): a log-sum-exp without the max '
+                         'shift in a density (the shifted form m + log(sum(exp(a - m))) '
+                         'of a Gaussian mixture lowers to the gmm target)')
+  if not any(_symbolic(v) for v in ops):
+    # no variable below: NumPy's own value on the host, a column again
+    raw = [v.col if isinstance(v, Val) else v for v in ops]
+    with np.errstate(all='ignore'):
+      return _operand(_apply(op, raw[0], lambda: raw[1]), OP_NAMES[op])
+  return Val(op, ops[0], None if b is None else ops[1], n=lens.pop() if lens else 0)
+
+
+def _reduce(v, name, args, kwargs):
+  """np.sum / np.mean (or the methods) of a vector, without options."""
+  if args or kwargs:
+    raise _not_lowerable('{} with options (axis=, dtype=, keepdims=, where=, '
+                         'out=) in a density'.format(name))
+  if not v.n:
+    raise _not_lowerable('{} of a scalar symbolic value (a reduction needs a '
+                         'data array) in a density'.format(name))
+  total = Val(SUM, v)
+  # np.mean: the pairwise sum, then a true divide by the count
+  return total if name.endswith('sum') else _mk(DIV, total, float(v.n))
 
 
 def _power(base, ex):
@@ -146,6 +254,8 @@ def _power(base, ex):
   if not isinstance(base, Val):
     raise _not_lowerable('** with a constant base in a density')
   c = _operand(ex, 'pow')
+  if isinstance(c, Val):
+    raise _not_lowerable('** with an array exponent in a density')
   if c == 2.0:
     return _mk(MUL, base, base)
   return _mk(POW, base, c)
@@ -153,12 +263,14 @@ def _power(base, ex):
 
 class Val:
   """A symbolic float64 scalar: arithmetic and the listed NumPy ufuncs on it
-  record nodes of a DAG (each Python object is evaluated once)."""
+  record nodes of a DAG (each Python object is evaluated once).  n > 0: a
+  vector of n observations, either a data column (col) or a value computed
+  from one; np.sum / np.mean of a vector is a scalar again (op SUM)."""
   __array_priority__ = 1000
-  __slots__ = ('op', 'a', 'b', 'var')
+  __slots__ = ('op', 'a', 'b', 'var', 'col', 'n')
 
-  def __init__(self, op, a=None, b=None, var=None):
-    self.op, self.a, self.b, self.var = op, a, b, var
+  def __init__(self, op, a=None, b=None, var=None, col=None, n=0):
+    self.op, self.a, self.b, self.var, self.col, self.n = op, a, b, var, col, n
 
   _UFUNCS = {np.add: ADD, np.subtract: SUB, np.multiply: MUL,
              np.true_divide: DIV, np.negative: NEG, np.absolute: ABS,
@@ -182,7 +294,17 @@ class Val:
     return _mk(self._UFUNCS[ufunc], *inputs)
 
   def __array_function__(self, func, types, args, kwargs):
-    raise _not_lowerable('np.{} in a scalar density'.format(func.__name__))
+    if func in (np.sum, np.mean) and args and args[0] is self:
+      return _reduce(self, 'np.' + func.__name__, args[1:], kwargs)
+    raise _not_lowerable('np.{} of a {} in a density (reductions: np.sum, np.mean '
+                         'of a data vector)'.format(
+                             func.__name__, 'data vector' if self.n else 'scalar'))
+
+  def sum(self, *args, **kwargs):
+    return _reduce(self, '.sum', args, kwargs)
+
+  def mean(self, *args, **kwargs):
+    return _reduce(self, '.mean', args, kwargs)
 
   def __bool__(self):
     raise _not_lowerable('truth value of a symbolic variable (a data-dependent '
@@ -217,9 +339,14 @@ class Val:
   def _unsupported(self, *a):
     raise _not_lowerable('operator without a kernel form in a density')
 
+  def _elements(self, *a):
+    raise _not_lowerable('iterating, indexing or len() of a {} in a density '
+                         '(the builtin sum iterates: use np.sum)'
+                         .format('data vector' if self.n else 'symbolic scalar'))
+
   __floordiv__ = __rfloordiv__ = __mod__ = __rmod__ = __matmul__ = _unsupported
-  __float__ = __int__ = __index__ = __iter__ = __len__ = _unsupported
-  __getitem__ = _unsupported
+  __float__ = __int__ = __index__ = _unsupported
+  __iter__ = __len__ = __getitem__ = _elements
 
 
 # scipy's own constants and operation order (_continuous_distns.py):
@@ -244,7 +371,7 @@ def _split(args, kwds, name):
   if set(kwds) - {'loc', 'scale'}:
     raise _not_lowerable('norm.{} with options in a density'.format(name))
   vals = [_operand(v, 'norm.' + name) for v in (x, loc, scale)]
-  return vals, any(isinstance(v, Val) for v in vals)
+  return vals, any(_symbolic(v) for v in vals)
 
 
 def _traced_logpdf(real):
@@ -278,7 +405,8 @@ def _traced_updf(real):
 
 def trace_expr(fn, keys):
   """A scalar density callable over the variables `keys` -> {'kind': 'expr',
-  'code': int32[], 'consts': float64[], 'depth': int}, or NotLowerable."""
+  'code': int32[], 'consts': float64[], 'depth': int}, or NotLowerable.  A
+  density that sums over 1-D data arrays also carries 'data' [C, n]."""
   from probayes_amd.lower import NotLowerable, _patched
   d = len(keys)
   if d > MAX_DIM:
@@ -302,18 +430,52 @@ def trace_expr(fn, keys):
       raise NotLowerable('density returned {}, not a scalar'
                          .format(type(out).__name__))
     out = c
+  elif out.n:
+    raise NotLowerable('density returned a vector of {} values unreduced (np.sum '
+                       'or np.mean makes it a scalar)'.format(out.n))
   return compile_dag(out, d)
 
 
 # ---------------------------------------------------------------------------
 # DAG -> program
 # ---------------------------------------------------------------------------
+def _computed(o):
+  """A node with an instruction of its own (not a variable, a data column or
+  a constant)."""
+  return isinstance(o, Val) and o.var is None and o.col is None
+
+
+def _region(total):
+  """The vector nodes under a SUM node in dependency order, and the scalar
+  nodes they read (which the outer program computes before the region)."""
+  body, outer, seen = [], [], set()
+  stack = [(total.a, False)]
+  while stack:
+    node, done = stack.pop()
+    if not _computed(node) or id(node) in seen:
+      continue
+    if not node.n:        # a scalar: the outer program's
+      seen.add(id(node))
+      outer.append(node)
+      continue
+    if done:
+      seen.add(id(node))
+      body.append(node)
+      continue
+    stack.append((node, True))
+    for o in (node.b, node.a):
+      stack.append((o, False))
+  return body, outer
+
+
 def compile_dag(root, d):
   """Linearises the DAG under `root` in dependency order (each node once),
   keeps a result in the accumulator when only the next instruction reads it,
-  and allocates slots by last use."""
+  and allocates slots by last use.  A SUM node becomes a loop region whose
+  body is linearised the same way over body temporaries."""
   from probayes_amd.lower import NotLowerable
   consts, cindex = [], {}
+  cols, colindex = [], {}
 
   def const(c):
     key = np.float64(c).tobytes()
@@ -322,9 +484,30 @@ def compile_dag(root, d):
       consts.append(np.float64(c))
     return (CONST, cindex[key])
 
+  def column(v):
+    key = v.col.tobytes()
+    if key not in colindex:
+      if cols and v.col.size != cols[0].size:   # two sums over different data
+        raise NotLowerable('data arrays of two lengths ({} and {}) in one density'
+                           .format(cols[0].size, v.col.size))
+      if len(cols) == MAX_COLS:
+        raise NotLowerable('density with more than {} data columns'.format(MAX_COLS))
+      colindex[key] = len(cols)
+      cols.append(v.col)
+    return (VAR, BODY_BASE + colindex[key])
+
+  regions = {}
+
+  def children(node):
+    if node.op == SUM:
+      if id(node) not in regions:
+        regions[id(node)] = _region(node)
+      return regions[id(node)][1]
+    return [o for o in (node.a, node.b) if _computed(o)]
+
   # post-order without recursion: operands before users, first use first
   order, index = [], {}
-  if isinstance(root, Val) and root.var is None:
+  if _computed(root):
     stack = [(root, False)]
     while stack:
       node, done = stack.pop()
@@ -335,40 +518,93 @@ def compile_dag(root, d):
         order.append(node)
         continue
       stack.append((node, True))
-      for o in (node.b, node.a):
-        if isinstance(o, Val) and o.var is None and id(o) not in index:
+      for o in reversed(children(node)):
+        if id(o) not in index:
           stack.append((o, False))
-  if len(order) > MAX_CODE:
+  n_words = sum(len(regions[id(v)][0]) + 2 if v.op == SUM else 1 for v in order)
+  if n_words > MAX_CODE:
     raise NotLowerable('expression of {} operations exceeds {} code words'
-                       .format(len(order), MAX_CODE))
+                       .format(n_words, MAX_CODE))
   users = [[] for _ in order]
   for i, node in enumerate(order):
-    for o in (node.a, node.b):
-      if isinstance(o, Val) and o.var is None:
-        users[index[id(o)]].append(i)
+    for o in children(node):
+      users[index[id(o)]].append(i)
   code, slot_of, free, depth = [], {}, [], 0
+
+  def body_words(total):
+    """The region of one SUM node: LOOP, the body, without the SUM word."""
+    body = regions[id(total)][0]
+    bindex = {id(v): j for j, v in enumerate(body)}
+    busers = [[] for _ in body]
+    for j, node in enumerate(body):
+      for o in (node.a, node.b):
+        if id(o) in bindex:
+          busers[bindex[id(o)]].append(j)
+    words, temp_of, tfree, n_temps = [], {}, [], 0
+    if not body:          # the sum of a column as it is
+      words.append(encode(MOV, column(total.a)))
+    for j, node in enumerate(body):
+      ops = []
+      for o in (node.a, node.b):
+        if o is None:
+          ops.append((SLOT, 0))
+        elif not isinstance(o, Val):
+          ops.append(const(o))
+        elif o.var is not None:
+          ops.append((VAR, o.var))
+        elif o.col is not None:
+          ops.append(column(o))
+        elif not o.n:     # computed by the outer program, kept in a slot
+          ops.append((SLOT, slot_of[index[id(o)]]))
+        elif bindex[id(o)] == j - 1:
+          ops.append((ACC, 0))
+        else:
+          ops.append((SLOT, BODY_BASE + temp_of[bindex[id(o)]]))
+      for o in {bindex[id(o)] for o in (node.a, node.b) if id(o) in bindex}:
+        if o in temp_of and max(busers[o]) == j:
+          tfree.append(temp_of.pop(o))
+      store = any(u != j + 1 for u in busers[j])
+      dst = 0
+      if store:
+        if tfree:
+          dst = min(tfree)
+          tfree.remove(dst)
+        else:
+          dst = n_temps
+          n_temps += 1
+          if n_temps > MAX_TEMPS:
+            raise NotLowerable('a sum whose terms keep more than {} intermediate '
+                               'vectors alive'.format(MAX_TEMPS))
+        temp_of[j] = dst
+      words.append(encode(node.op, ops[0], ops[1], dst, store))
+    return [encode(LOOP, (SLOT, len(words)))] + words
+
   if not order:   # a bare variable or a constant
     src = (VAR, root.var) if isinstance(root, Val) else const(root)
     code.append(encode(MOV, src))
   for i, node in enumerate(order):
     ops = []
-    for o in (node.a, node.b):
-      if o is None:
-        ops.append((SLOT, 0))
-      elif not isinstance(o, Val):
-        ops.append(const(o))
-      elif o.var is not None:
-        ops.append((VAR, o.var))
-      elif index[id(o)] == i - 1:
-        ops.append((ACC, 0))
-      else:
-        ops.append((SLOT, slot_of[index[id(o)]]))
+    if node.op == SUM:
+      code += body_words(node)
+      ops = [(ACC, 0), (SLOT, 0)]
+    else:
+      for o in (node.a, node.b):
+        if o is None:
+          ops.append((SLOT, 0))
+        elif not isinstance(o, Val):
+          ops.append(const(o))
+        elif o.var is not None:
+          ops.append((VAR, o.var))
+        elif index[id(o)] == i - 1:
+          ops.append((ACC, 0))
+        else:
+          ops.append((SLOT, slot_of[index[id(o)]]))
     # slots whose last reader is this instruction are free for its result
-    for o in {index[id(o)] for o in (node.a, node.b)
-              if isinstance(o, Val) and o.var is None}:
+    for o in {index[id(o)] for o in children(node)}:
       if o in slot_of and max(users[o]) == i:
         free.append(slot_of.pop(o))
-    store = any(u != i + 1 for u in users[i])
+    # a region's body has an accumulator of its own: what it reads is in a slot
+    store = any(u != i + 1 or order[u].op == SUM for u in users[i])
     dst = 0
     if store:
       if free:
@@ -385,31 +621,70 @@ def compile_dag(root, d):
   if len(consts) > MAX_CONSTS:
     raise NotLowerable('expression with {} constants exceeds {}'
                        .format(len(consts), MAX_CONSTS))
-  return {'kind': 'expr', 'code': np.asarray(code, np.int32),
-          'consts': np.asarray(consts, np.float64), 'depth': int(depth)}
+  out = {'kind': 'expr', 'code': np.asarray(code, np.int32),
+         'consts': np.asarray(consts, np.float64), 'depth': int(depth)}
+  if cols:
+    out['data'] = np.stack(cols)
+  return out
 
 
-def check_program(code, consts, depth, d):
-  """The checks pbh_set_model makes (ValueError with the cause)."""
+def check_program(code, consts, depth, d, data=None):
+  """The checks pbh_set_model makes (ValueError with the cause).  data: the
+  [C, n] block of a program with loop regions."""
   code = np.asarray(code).reshape(-1)
   n_consts = np.asarray(consts).size
   if not 1 <= code.size <= MAX_CODE:
     raise ValueError('expr: {} code words outside 1..{}'.format(code.size, MAX_CODE))
   if n_consts > MAX_CONSTS or not 0 <= depth <= MAX_SLOTS or not 1 <= d <= MAX_DIM:
     raise ValueError('expr: constants / depth / dim over the limits')
+  n_cols = 0
+  if data is not None:
+    data = np.asarray(data)
+    if data.ndim != 2 or not 1 <= data.shape[0] <= MAX_COLS or \
+       not 1 <= data.shape[1] <= MAX_OBS:
+      raise ValueError('expr: data of shape {} outside [1..{}, 1..{}]'
+                       .format(data.shape, MAX_COLS, MAX_OBS))
+    n_cols = data.shape[0]
   written = set()
+  end = -1          # the SUM word of the open region, -1 outside one
   for pc, w in enumerate(code):
     if w < 0:
       raise ValueError('expr: bad code word at {}'.format(pc))
     op, dst, store, a, b = decode(w)
-    if op >= N_OPS:
+    if op == LOOP:
+      if end >= 0:
+        raise ValueError('expr: nested loop region at {}'.format(pc))
+      if n_cols == 0:
+        raise ValueError('expr: loop region without data at {}'.format(pc))
+      end = pc + a[1] + 1
+      if a[1] < 1 or end >= code.size or decode(code[end])[0] != SUM:
+        raise ValueError('expr: loop region at {} does not end in SUM'.format(pc))
+      first, temps = pc + 1, set()
+      continue
+    if op == SUM:
+      if pc != end or a != (ACC, 0):
+        raise ValueError('expr: SUM outside a loop region at {}'.format(pc))
+      end = -1
+    elif op >= N_OPS:
       raise ValueError('expr: bad opcode {} at {}'.format(op, pc))
-    for kind, i in (a, b)[:ARITY[op]]:
-      ok = (kind == SLOT and i in written) or (kind == VAR and i < d) or \
-           (kind == CONST and i < n_consts) or (kind == ACC and pc > 0)
+    body = end >= 0
+    for kind, i in (a, b)[:1 if op == SUM else ARITY[op]]:
+      if body:
+        ok = (kind == SLOT and (i - BODY_BASE in temps if i >= BODY_BASE
+                                else i in written)) or \
+             (kind == VAR and (i - BODY_BASE < n_cols if i >= BODY_BASE else i < d)) or \
+             (kind == CONST and i < n_consts) or (kind == ACC and pc > first)
+      else:
+        ok = (kind == SLOT and i in written) or (kind == VAR and i < d) or \
+             (kind == CONST and i < n_consts) or (kind == ACC and pc > 0)
       if not ok:
         raise ValueError('expr: bad operand ({}, {}) at {}'.format(kind, i, pc))
-    if store:
+    if store and body:
+      if dst >= MAX_TEMPS:
+        raise ValueError('expr: body temporary {} >= {} at {} (a body writes no '
+                         'outer slot)'.format(dst, MAX_TEMPS, pc))
+      temps.add(dst)
+    elif store:
       if dst >= depth:
         raise ValueError('expr: slot {} >= depth {} at {}'.format(dst, depth, pc))
       written.add(dst)

@@ -23,6 +23,7 @@ Recognised forms
          any other scalar expression of the variables in + - * / ** abs,
          exp log sqrt log1p expm1 square maximum minimum and
          norm.logpdf / norm.pdf (probayes_amd/expr.py)           -> expr
+         ... and of 1-D data arrays, summed with np.sum / np.mean  -> expr with data
   plus the scipy objects themselves (norm.pdf/logpdf, uniform.pdf,
   multivariate_normal) and the descriptor callables of probayes_amd.models.
 """

@@ -13,7 +13,8 @@ encodes the closed set of model forms the engine lowers:
                 mvn         multivariate_normal.pdf at the permuted vector (lin)
                 expr        any scalar expression of the variables, as a program
                             {code, consts, depth} the kernels interpret
-                            (probayes_amd/expr.py; pscale as declared)
+                            (probayes_amd/expr.py; pscale as declared); with
+                            data [C, n]: sums over n observations of C columns
   prior         joint=True uniform prior of the root RVs (rv_utils.py:8-47)
   ufun          per-dim 1 = (log, exp) change of variable (variable.py:693-697)
   proposal kind gauss   callable Delta(norm.rvs(loc, scale)) per dim
@@ -94,7 +95,13 @@ def make_spec(dim, target, proposal, scores='hastings', pscale=None,
     target['code'] = np.asarray(target['code'], dtype=np.int32).reshape(-1)
     target['consts'] = np.asarray(target['consts'], dtype=np.float64).reshape(-1)
     target['depth'] = int(target['depth'])
-    expr.check_program(target['code'], target['consts'], target['depth'], d)
+    if target.get('data') is not None:   # [C, n]: the columns of the loop regions
+      target['data'] = np.ascontiguousarray(
+          np.atleast_2d(np.asarray(target['data'], dtype=np.float64)))
+    else:
+      target.pop('data', None)
+    expr.check_program(target['code'], target['consts'], target['depth'], d,
+                       target.get('data'))
   if prior is not None:
     prior = dict(prior)
     prior['lo'] = _vec(prior['lo'], d, 'prior.lo')

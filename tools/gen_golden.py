@@ -51,9 +51,10 @@ def _pb():
 from mcmc_examples import WORKLOADS, TFUN_WORKLOADS, DELTA_WORKLOADS, \
     SEGMENTED  # noqa: E402
 from expr_examples import EXPR_WORKLOADS  # noqa: E402
+from expr_data_examples import DATA_WORKLOADS  # noqa: E402
 # builders shared with tests
 WORKLOADS = dict(WORKLOADS, **TFUN_WORKLOADS, **DELTA_WORKLOADS,
-                 **EXPR_WORKLOADS)
+                 **EXPR_WORKLOADS, **DATA_WORKLOADS)
 
 
 def _nan(v):
