@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from probayes_amd import _lib
+from philox_host import bm96_host as _bm96_host, u01 as _u01
 
 pytestmark = pytest.mark.gpu
 
@@ -18,11 +19,6 @@ def _normals(words):
   _lib.call('pbh_check_normals', 0, n, words.ctypes.data_as(_lib._u32p),
             fast.ctypes.data_as(_lib._dp), ref.ctypes.data_as(_lib._dp))
   return fast, ref
-
-
-def _u01(a, b):
-  return ((a >> 5).astype(np.float64) * 67108864.0 +
-          (b >> 6).astype(np.float64)) / 9007199254740992.0
 
 
 def test_fast_box_muller_matches_libm_and_numpy():
@@ -56,19 +52,6 @@ def _normals64(words):
   _lib.call('pbh_check_normals64', 0, n, words.ctypes.data_as(_lib._u32p),
             fast.ctypes.data_as(_lib._dp), ref.ctypes.data_as(_lib._dp))
   return fast, ref
-
-
-def _bm96_host(w):
-  """bm96_pair's construction in NumPy (pbh_device.h): u1 = (k1 + 1/2)
-  2^-52 from b[31:12]:a, the full-turn angle (J + c 2^-32) 2 pi / 1024 with
-  J = b[11:2]."""
-  w = w.astype(np.uint64)
-  k1 = ((w[:, 1] >> 12) << 32) | w[:, 0]
-  u1 = (k1.astype(np.float64) + 0.5) * 2.0 ** -52
-  j = ((w[:, 1] >> 2) & 0x3FF).astype(np.float64)
-  ang = (j + w[:, 2].astype(np.float64) * 2.0 ** -32) * (2 * np.pi / 1024)
-  r = np.sqrt(-2.0 * np.log(u1))
-  return np.stack([r * np.cos(ang), r * np.sin(ang)], 1), r
 
 
 def _words96(rng, n):

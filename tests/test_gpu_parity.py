@@ -558,6 +558,7 @@ def test_iid_steady_state_form_is_the_general_form(monkeypatch, pair, n):
     eng = Engine(spec)
     eng.init_chains(init)
     eng.set_rng('philox', seed=13)
+    eng.set_collect(moments=False)   # the steady-state forms keep no moments
     eng.alloc_trace(t, 1)
     eng.run(1)
     eng.run(4, steps_per_launch=1)
@@ -592,6 +593,7 @@ def test_pair_steady_state_form_is_the_general_form(monkeypatch, which):
     eng = Engine(spec)
     eng.init_chains(init)
     eng.set_rng('philox', seed=11)
+    eng.set_collect(moments=False)   # FULL is launched only without moments
     eng.alloc_trace(t, 1)
     eng.run(1)
     eng.run(4, steps_per_launch=1)
