@@ -81,7 +81,7 @@ hipError_t launch_mh(const KArgs &a, hipStream_t s, size_t lds) {
 #undef PBH_CASE
     default:   // d = 13..15 exist for the expression target alone
       if (a.target != PBH_TARGET_EXPR) return hipErrorInvalidValue;
-      return a.edata ? launch_mh_expr_data(a, s) : launch_mh_expr(a, s);
+      return launch_mh_expr(a, s);
   }
 }
 

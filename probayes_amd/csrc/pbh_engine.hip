@@ -23,6 +23,7 @@
 
 #include "../../include/pbhip.h"
 #include "pbh_kernels.h"
+#include "pbh_expr_host.h"
 #include "pbh_device.h"
 
 using pbh::KArgs;
@@ -782,147 +783,11 @@ int pbh_cache_info(int64_t *idle_bytes, int64_t *hits, int64_t *misses) {
 // ---------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------
-// PBH_TARGET_EXPR: the program is checked here, on the host, so that the
-// interpreter may trust it (pbhip.h): every opcode, every operand's index
-// for its kind, a slot or the accumulator read only after it was written,
-// and the limits.  Returns nullptr, or what is wrong (pc: where).
-static const char *expr_check(int d, const int32_t *code, int32_t n_code,
-                              const double *consts, int32_t n_consts, int32_t depth,
-                              int *pc_out, const double *data = nullptr,
-                              int32_t n_cols = 0, int32_t n_obs = 0) {
-  *pc_out = -1;
-  if (d < 1 || d > PBH_EXPR_MAX_DIM) return "dim outside 1..16";
-  if (!code || n_code < 1 || n_code > PBH_EXPR_MAX_CODE) return "code words outside 1..256";
-  if (n_consts < 0 || n_consts > PBH_EXPR_MAX_CONSTS || (n_consts && !consts))
-    return "constants outside 0..128 (or missing)";
-  if (depth < 0 || depth > PBH_EXPR_MAX_SLOTS) return "depth outside 0..16";
-  if (data || n_cols || n_obs) {
-    if (!data) return "data columns missing";
-    if (n_cols < 1 || n_cols > PBH_EXPR_MAX_COLS) return "data columns outside 1..8";
-    if (n_obs < 1 || n_obs > PBH_EXPR_MAX_OBS) return "observations outside 1..65536";
-  }
-  uint32_t written = 0, temps = 0;
-  int end = -1, first = 0;   // the open region's SUM word (-1: none), its first word
-  for (int pc = 0; pc < n_code; ++pc) {
-    *pc_out = pc;
-    if (code[pc] < 0) return "code word with bit 31 set";
-    const uint32_t w = (uint32_t)code[pc], op = w & 63u;
-    if (op == PBH_EXPR_LOOP) {
-      if (end >= 0) return "nested loop region";
-      if (!data) return "loop region in a program without data";
-      const int len = (int)((w >> 13) & 255u);
-      end = pc + len + 1;
-      if (len < 1 || end >= n_code || code[end] < 0 ||
-          ((uint32_t)code[end] & 63u) != PBH_EXPR_SUM)
-        return "loop region does not end in SUM";
-      first = pc + 1;
-      temps = 0;
-      continue;
-    }
-    const bool sum = op == PBH_EXPR_SUM;
-    if (sum) {
-      if (pc != end || ((w >> 11) & 3u) != PBH_EXPR_ACC) return "SUM outside a loop region";
-      end = -1;
-    } else if (op >= PBH_EXPR_N_OPS) {
-      return "unknown opcode";
-    }
-    const bool body = end >= 0;
-    const bool binary = !sum && ((op >= PBH_EXPR_ADD && op <= PBH_EXPR_DIV) || op >= PBH_EXPR_MAX);
-    for (int j = 0; j < (binary ? 2 : 1); ++j) {
-      const uint32_t kind = (w >> (j ? 21 : 11)) & 3u, idx = (w >> (j ? 23 : 13)) & 255u;
-      if (body && idx >= PBH_EXPR_BODY_BASE && kind == PBH_EXPR_SLOT) {
-        const uint32_t t = idx - PBH_EXPR_BODY_BASE;
-        if (!(t < PBH_EXPR_MAX_TEMPS && ((temps >> t) & 1u)))
-          return "body temporary read before the body wrote it (or outside the 4)";
-        continue;
-      }
-      if (body && idx >= PBH_EXPR_BODY_BASE && kind == PBH_EXPR_VAR) {
-        if (idx - PBH_EXPR_BODY_BASE >= (uint32_t)n_cols) return "data column out of range";
-        continue;
-      }
-      if (kind == PBH_EXPR_SLOT && !(idx < (uint32_t)depth && ((written >> idx) & 1u)))
-        return "slot read before it is written (or outside the depth)";
-      if (kind == PBH_EXPR_VAR && idx >= (uint32_t)d) return "variable index outside the dims";
-      if (kind == PBH_EXPR_CONST && idx >= (uint32_t)n_consts) return "constant index out of range";
-      if (kind == PBH_EXPR_ACC && pc == (body ? first : 0))
-        return body ? "accumulator read by a body's first word"
-                    : "accumulator read by the first instruction";
-    }
-    if ((w >> 10) & 1u) {
-      const uint32_t dst = (w >> 6) & 15u;
-      if (body) {   // the store field names a body temporary: no outer slot is written
-        if (dst >= PBH_EXPR_MAX_TEMPS) return "body stores outside its 4 temporaries";
-        temps |= 1u << dst;
-      } else {
-        if (dst >= (uint32_t)depth) return "stored slot outside the depth";
-        written |= 1u << dst;
-      }
-    }
-  }
-  return nullptr;
-}
-
-// The leaves of NumPy's pairwise_sum over the terms [s, s + m) in order
-// (numpy/core/src/umath/loops_utils.h: at most 128 terms are a leaf, else
-// the left half rounded down to a multiple of 8, then the rest), each with
-// the number of pending left sums its result is added to: `pops` counts the
-// ancestors this subtree is the right child of.  Returns the deepest stack.
-static int expr_leaves(std::vector<uint32_t> &out, int s, int m, int pops, int pending) {
-  if (m <= 128) {
-    out.push_back(pbh::expr_leaf_word(s, m, pops));
-    return pending + 1;
-  }
-  int m2 = m / 2;
-  m2 -= m2 % 8;
-  const int dl = expr_leaves(out, s, m2, 0, pending);
-  const int dr = expr_leaves(out, s + m2, m - m2, pops + 1, pending + 1);
-  return dl > dr ? dl : dr;
-}
-
-// The data of a program with regions into the block: the columns, each padded
-// with zeros to a multiple of 8 observations, from an offset that is a
-// multiple of 8 doubles (64 bytes: the block itself is 256-byte aligned), then
-// the leaf words.  Returns the columns' offset.
-struct ExprData {
-  size_t odata = 0, oleaf = 0;
-  int32_t npad = 0, nleaf = 0;
-};
-static ExprData expr_data_pack(std::vector<double> &blk, const double *data, int32_t n_cols,
-                               int32_t n_obs) {
-  ExprData o;
-  blk.resize((blk.size() + 7) / 8 * 8, 0.0);
-  o.odata = blk.size();
-  o.npad = (n_obs + 7) / 8 * 8;
-  blk.resize(o.odata + (size_t)n_cols * o.npad, 0.0);
-  for (int c = 0; c < n_cols; ++c)
-    std::memcpy(&blk[o.odata + (size_t)c * o.npad], data + (size_t)c * n_obs,
-                (size_t)n_obs * sizeof(double));
-  std::vector<uint32_t> leaves;
-  const int deepest = expr_leaves(leaves, 0, n_obs, 0, 0);
-  (void)deepest;   // <= 10 at PBH_EXPR_MAX_OBS terms (kExprLeafStack = 12)
-  o.nleaf = (int32_t)leaves.size();
-  o.oleaf = blk.size();
-  blk.resize(o.oleaf + (leaves.size() + 1) / 2, 0.0);
-  std::memcpy(&blk[o.oleaf], leaves.data(), leaves.size() * sizeof(uint32_t));
-  return o;
-}
-
 // PBH_EXPR_DATA_WIDE=0: the bodies one observation at a time (the comparison
 // form; the default decodes a body word once per block of 8 observations)
 static int32_t expr_data_wide() {
   const char *v = std::getenv("PBH_EXPR_DATA_WIDE");
   return (v && v[0] == '0') ? 0 : 1;
-}
-
-// the program into a block of doubles: 256 constants (padded with zeros),
-// then 256 code words (padded with MOV words); returns the constants' offset
-static size_t expr_pack(std::vector<double> &blk, const int32_t *code, int32_t n_code,
-                        const double *consts, int32_t n_consts) {
-  const size_t o = blk.size();
-  blk.resize(o + 256 + PBH_EXPR_MAX_CODE / 2, 0.0);
-  for (int i = 0; i < n_consts; ++i) blk[o + i] = consts[i];
-  std::memcpy(&blk[o + 256], code, (size_t)n_code * sizeof(int32_t));
-  return o;
 }
 
 int pbh_set_model(pbh_engine *e, const pbh_model *m) {
@@ -945,6 +810,7 @@ int pbh_set_model(pbh_engine *e, const pbh_model *m) {
     return fail(PBH_ERR_STATE, "dim %d differs from initialised chains (%d)",
                 d, e->d);
   std::vector<double> blk;
+  pbh::ExprProgram prog;
   size_t oa = 0, ob = 0, oc = 0, oe = 0, oplo = 0, ophi = 0, otoff = 0;
   const double *A = m->a, *B = m->b, *C = m->c, *E = m->e;
   int64_t na = 0, nb = 0, nc = 0, ne = 0;
@@ -964,10 +830,10 @@ int pbh_set_model(pbh_engine *e, const pbh_model *m) {
     case PBH_TARGET_UNIFORM_PDF: na = nb = d; break;
     case PBH_TARGET_MVN: na = d; nb = (int64_t)d * d; nc = 1; break;
     case PBH_TARGET_EXPR: {
+      prog = {d, m->expr_code, m->expr_n_code, m->expr_consts, m->expr_n_consts,
+              m->expr_depth, m->expr_data, m->expr_n_cols, m->expr_n_obs};
       int pc = -1;
-      if (const char *why = expr_check(d, m->expr_code, m->expr_n_code, m->expr_consts,
-                                       m->expr_n_consts, m->expr_depth, &pc, m->expr_data,
-                                       m->expr_n_cols, m->expr_n_obs))
+      if (const char *why = pbh::expr_check(prog, &pc))
         return fail(PBH_ERR_ARG, "expression program: %s (code word %d)", why, pc);
       break;
     }
@@ -1014,12 +880,7 @@ int pbh_set_model(pbh_engine *e, const pbh_model *m) {
     const double st[2] = {mean, s2};
     ow = pack(blk, st, 2);
   }
-  size_t oexpr = 0;
-  if (is_expr)
-    oexpr = expr_pack(blk, m->expr_code, m->expr_n_code, m->expr_consts, m->expr_n_consts);
-  const bool has_data = is_expr && m->expr_data;
-  ExprData ed;
-  if (has_data) ed = expr_data_pack(blk, m->expr_data, m->expr_n_cols, m->expr_n_obs);
+  const pbh::ExprLayout lay = is_expr ? pbh::expr_pack(blk, prog) : pbh::ExprLayout{};
   uint32_t lo_incl = 0, hi_incl = 0, ufun = 0;
   if (m->has_prior) {
     if (!m->prior_lo || !m->prior_hi || !m->prior_lo_incl || !m->prior_hi_incl)
@@ -1061,14 +922,7 @@ int pbh_set_model(pbh_engine *e, const pbh_model *m) {
   k.d = d; k.target = m->target_kind; k.pscale = m->pscale; k.scores = m->scores;
   k.ta = base + oa; k.tb = base + ob; k.tc = base + oc; k.te = base + oe;
   k.tw = base + ow; k.ksum = ksum;
-  k.econst = is_expr ? base + oexpr : nullptr;
-  k.ecode = is_expr ? reinterpret_cast<const int32_t *>(base + oexpr + 256) : nullptr;
-  k.en = is_expr ? m->expr_n_code : 0;
-  k.edata = has_data ? base + ed.odata : nullptr;
-  k.eleaf = has_data ? reinterpret_cast<const int32_t *>(base + ed.oleaf) : nullptr;
-  k.enobs = has_data ? m->expr_n_obs : 0;
-  k.enpad = ed.npad;
-  k.enleaf = ed.nleaf;
+  pbh::expr_bind(k, base, lay);
   k.ewide = expr_data_wide();
   k.tn = (m->target_kind == PBH_TARGET_NORM_IID || m->target_kind == PBH_TARGET_GMM) ? m->n : 0;
   k.i0 = m->i0; k.i1 = m->i1;
@@ -2814,21 +2668,17 @@ int pbh_check_accept(int device, int64_t n, const double *lp,
   return PBH_OK;
 }
 
-static int eval_expr_impl(const char *fn, int device, int32_t d, const int32_t *code,
-                          int32_t n_code, const double *consts, int32_t n_consts,
-                          int32_t depth, const double *data, int32_t n_cols, int32_t n_obs,
-                          int64_t n, const double *x, double *out) {
+static int eval_expr_impl(const char *fn, int device, const pbh::ExprProgram &p, int64_t n,
+                          const double *x, double *out) {
   if (check_ptr(x, "x") || check_ptr(out, "out")) return PBH_ERR_ARG;
   if (n <= 0) return fail(PBH_ERR_ARG, "n must be positive");
   int pc = -1;
-  if (const char *why = expr_check(d, code, n_code, consts, n_consts, depth, &pc, data,
-                                   n_cols, n_obs))
+  if (const char *why = pbh::expr_check(p, &pc))
     return fail(PBH_ERR_ARG, "expression program: %s (code word %d)", why, pc);
   HIP_TRY(hipSetDevice(device));
   std::vector<double> blk;
-  expr_pack(blk, code, n_code, consts, n_consts);
-  ExprData ed;
-  if (data) ed = expr_data_pack(blk, data, n_cols, n_obs);
+  const pbh::ExprLayout lay = pbh::expr_pack(blk, p);
+  const int32_t d = p.d;
   std::vector<double> xt((size_t)d * n);   // [n][d] -> [d][n]
   for (int64_t i = 0; i < n; ++i)
     for (int k = 0; k < d; ++k) xt[(size_t)k * n + i] = x[(size_t)i * d + k];
@@ -2845,20 +2695,9 @@ static int eval_expr_impl(const char *fn, int device, int32_t d, const int32_t *
       KArgs k{};
       k.d = d;
       k.target = PBH_TARGET_EXPR;
-      k.econst = dblk;
-      k.ecode = reinterpret_cast<const int32_t *>(dblk + 256);
-      k.en = n_code;
-      if (data) {
-        k.edata = dblk + ed.odata;
-        k.eleaf = reinterpret_cast<const int32_t *>(dblk + ed.oleaf);
-        k.enobs = n_obs;
-        k.enpad = ed.npad;
-        k.enleaf = ed.nleaf;
-        k.ewide = expr_data_wide();
-        err = pbh::launch_eval_expr_data(k, n, dx, dout);
-      } else {
-        err = pbh::launch_eval_expr(k, n, dx, dout);
-      }
+      pbh::expr_bind(k, dblk, lay);
+      k.ewide = expr_data_wide();
+      err = pbh::launch_eval_expr(k, n, dx, dout);
     }
     if (err == hipSuccess) err = hipMemcpy(out, dout, n * sizeof(double), hipMemcpyDeviceToHost);
   }
@@ -2872,8 +2711,8 @@ static int eval_expr_impl(const char *fn, int device, int32_t d, const int32_t *
 int pbh_eval_expr(int device, int32_t d, const int32_t *code, int32_t n_code,
                   const double *consts, int32_t n_consts, int32_t depth, int64_t n,
                   const double *x, double *out) {
-  return eval_expr_impl("pbh_eval_expr", device, d, code, n_code, consts, n_consts, depth,
-                        nullptr, 0, 0, n, x, out);
+  return eval_expr_impl("pbh_eval_expr", device,
+                        {d, code, n_code, consts, n_consts, depth, nullptr, 0, 0}, n, x, out);
 }
 
 int pbh_eval_expr_data(int device, int32_t d, const int32_t *code, int32_t n_code,
@@ -2881,8 +2720,9 @@ int pbh_eval_expr_data(int device, int32_t d, const int32_t *code, int32_t n_cod
                        const double *data, int32_t n_cols, int32_t n_obs, int64_t n,
                        const double *x, double *out) {
   if (check_ptr(data, "data")) return PBH_ERR_ARG;
-  return eval_expr_impl("pbh_eval_expr_data", device, d, code, n_code, consts, n_consts,
-                        depth, data, n_cols, n_obs, n, x, out);
+  return eval_expr_impl("pbh_eval_expr_data", device,
+                        {d, code, n_code, consts, n_consts, depth, data, n_cols, n_obs}, n, x,
+                        out);
 }
 
 int pbh_bool_perm_freq(int device, int64_t rows, int32_t cols,

@@ -7,6 +7,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include "pbh_expr_words.h"
+
 namespace pbh {
 
 // Dispatch timing of pbh_run's timed region: the start / stop events ride on
@@ -165,13 +167,6 @@ struct KArgs {
 // stays PBH_TARGET_EXPR, the kernels compiled with this constant hold the
 // interpreter with regions (pbh_expr_data.hip)
 constexpr int kTargetExprData = 8;
-// One leaf of the pairwise sum (NumPy's pairwise_sum: a block of at most 128
-// terms that starts at a multiple of 8): start / 8 | terms << 13 | pops << 21,
-// pops = the pending left sums this leaf's result is then added to.
-constexpr int kExprLeafStack = 12;   // pending sums: 10 at 65 536 terms
-inline uint32_t expr_leaf_word(int start, int terms, int pops) {
-  return (uint32_t)(start / 8) | ((uint32_t)terms << 13) | ((uint32_t)pops << 21);
-}
 // The resident server's host command block and completion words (engine:
 // pbh_server_*, kernel: mh_pair_kernel<..., SRV>).  The host writes the
 // fields, then seq (release).  Workgroup 0's first wave alone polls the host
@@ -217,14 +212,10 @@ hipError_t launch_mh_server(const KArgs &a, hipStream_t s, int32_t *wgs, bool ch
 hipError_t launch_xo_seed(uint32_t *xo, int64_t n, int64_t off, uint64_t seed,
                           hipStream_t s);
 bool mh_dim_supported(int d);
-// PBH_TARGET_EXPR: mh_kernel<D, RNG, PBH_TARGET_EXPR, 0>, d = 1..16
-// (pbh_expr.hip); launch_eval_expr evaluates the program at x [d][n]
+// PBH_TARGET_EXPR: mh_kernel<D, RNG, PBH_TARGET_EXPR, 0>, d = 1..16, or with loop regions
+// (a.edata) <D, RNG, kTargetExprData, 0>; launch_eval_expr: the program at x [d][n]
 hipError_t launch_mh_expr(const KArgs &a, hipStream_t s);
 hipError_t launch_eval_expr(const KArgs &a, int64_t n, const double *x, double *out);
-// the same for a program with loop regions: mh_kernel<D, RNG,
-// kTargetExprData, 0>, d = 1..16 (pbh_expr_data.hip)
-hipError_t launch_mh_expr_data(const KArgs &a, hipStream_t s);
-hipError_t launch_eval_expr_data(const KArgs &a, int64_t n, const double *x, double *out);
 hipError_t launch_check_normals(int64_t n, const uint32_t *words, double *fast,
                                 double *ref);
 // bm96_pair (the production fp64 normals) and its libm form on n word triples.

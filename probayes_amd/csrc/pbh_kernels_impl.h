@@ -193,12 +193,10 @@ __device__ __forceinline__ double gmm_fast(const KArgs &a, const double (&x)[D])
   return m + log(sum);
 }
 
-// PBH_TARGET_EXPR: the density is a program (expr_density below)
-template <int D>
+// PBH_TARGET_EXPR: the density is a program, DATA: with loop regions
+// (pbh_expr_impl.h, which the expression units alone include)
+template <int D, bool DATA>
 __device__ __forceinline__ double expr_density(const KArgs &a, const double (&x)[D]);
-// ... with loop regions over data (defined in pbh_expr_data.hip alone)
-template <int D>
-__device__ __forceinline__ double expr_data_density(const KArgs &a, const double (&x)[D]);
 
 // lx (production, may be null): log of x for the dims with the (log, exp)
 // ufun, as the proposal formed them (x' = exp(log x + delta)), so the
@@ -334,11 +332,11 @@ __device__ __forceinline__ double joint_density(const KArgs &a,
     case PBH_TARGET_EXPR:
       // only in the kernels compiled for it (mh_kernel<D, RNG, EXPR, 0>,
       // which launch_mh_d always takes for this target)
-      if constexpr (TGT == PBH_TARGET_EXPR) out = expr_density<D>(a, x);
+      if constexpr (TGT == PBH_TARGET_EXPR) out = expr_density<D, false>(a, x);
       else out = __builtin_nan("");
       break;
     case kTargetExprData:   // never a.target: mh_kernel<D, RNG, kTargetExprData, 0>
-      if constexpr (TGT == kTargetExprData) out = expr_data_density<D>(a, x);
+      if constexpr (TGT == kTargetExprData) out = expr_density<D, true>(a, x);
       else out = __builtin_nan("");
       break;
     default:
@@ -426,79 +424,6 @@ __device__ __forceinline__ double np_minimum(double a, double b) {
 }
 __device__ __forceinline__ double np_maximum(double a, double b) {
   return (a != a || b != b) ? a + b : (a > b ? a : b);
-}
-
-// ---------------------------------------------------------------------------
-// PBH_TARGET_EXPR: the interpreter of a density given as a program (pbhip.h
-// pbh_expr_op; probayes_amd/expr.py evaluate() is the NumPy definition).
-// Every lane runs the same program on its own chain, so the program counter,
-// the code word and every decoded field are wave-uniform: the word is a scalar
-// load through the constant address space, the opcode dispatch a scalar
-// branch.  The previous result stays in a register (acc); results needed
-// later live in LDS slots laid out [slot][thread] (conflict-free, 2 KB per
-// slot and workgroup), never in a runtime-indexed private array.  A variable
-// is fetched with the unrolled select on a uniform index.  The host checked
-// the program (pbh_set_model); the index masks only keep a wrong word inside
-// the slot block and the padded constant block.  -ffp-contract=off: + - * /
-// are the IEEE operations NumPy performs; exp / log / log1p / expm1 / pow are
-// OCML's in every RNG mode.
-// ---------------------------------------------------------------------------
-constexpr int kExprSlots = PBH_EXPR_MAX_SLOTS;
-constexpr int kExprConstPad = 256;   // doubles the engine reserves for constants
-
-__device__ __forceinline__ uint32_t cldw(const int32_t *p, int i) {
-  return (uint32_t)((const __attribute__((address_space(4))) int32_t *)p)[i];
-}
-
-template <int D>
-__device__ __forceinline__ double expr_operand(const KArgs &a, const double (&x)[D],
-                                               const double *sl, double acc,
-                                               uint32_t kind, uint32_t idx) {
-  if (kind == PBH_EXPR_SLOT) return sl[(idx & (kExprSlots - 1)) * kBlock];
-  if (kind == PBH_EXPR_CONST) return cld(a.econst, idx & (kExprConstPad - 1));
-  if (kind == PBH_EXPR_ACC) return acc;
-  double v = 0.;
-#pragma unroll
-  for (int k = 0; k < D; ++k)
-    if (k == (int)idx) v = x[k];
-  return v;
-}
-
-template <int D>
-__device__ __forceinline__ double expr_density(const KArgs &a, const double (&x)[D]) {
-  __shared__ double s_expr[kExprSlots * kBlock];
-  double *const sl = s_expr + threadIdx.x;
-  double acc = 0.;
-  const int n = a.en;
-  for (int pc = 0; pc < n; ++pc) {
-    const uint32_t w = __builtin_amdgcn_readfirstlane(cldw(a.ecode, pc));
-    const uint32_t op = w & 63u;
-    const double va = expr_operand<D>(a, x, sl, acc, (w >> 11) & 3u, (w >> 13) & 255u);
-    double vb = 0.;
-    if ((op >= PBH_EXPR_ADD && op <= PBH_EXPR_DIV) || op >= PBH_EXPR_MAX)
-      vb = expr_operand<D>(a, x, sl, acc, (w >> 21) & 3u, (w >> 23) & 255u);
-    double r;
-    switch (op) {
-      case PBH_EXPR_ADD: r = va + vb; break;
-      case PBH_EXPR_SUB: r = va - vb; break;
-      case PBH_EXPR_MUL: r = va * vb; break;
-      case PBH_EXPR_DIV: r = va / vb; break;
-      case PBH_EXPR_NEG: r = -va; break;
-      case PBH_EXPR_ABS: r = __builtin_fabs(va); break;
-      case PBH_EXPR_SQRT: r = sqrt(va); break;
-      case PBH_EXPR_EXP: r = exp(va); break;
-      case PBH_EXPR_LOG: r = log(va); break;
-      case PBH_EXPR_LOG1P: r = log1p(va); break;
-      case PBH_EXPR_EXPM1: r = expm1(va); break;
-      case PBH_EXPR_MAX: r = np_maximum(va, vb); break;
-      case PBH_EXPR_MIN: r = np_minimum(va, vb); break;
-      case PBH_EXPR_POW: r = pow(va, vb); break;
-      default: r = va; break;   // PBH_EXPR_MOV
-    }
-    acc = r;
-    if ((w >> 10) & 1u) sl[((w >> 6) & (kExprSlots - 1)) * kBlock] = r;
-  }
-  return acc;
 }
 
 // bound=True on one scalar value (variable.py:711-728): closed limits clamp;
@@ -3665,11 +3590,10 @@ hipError_t launch_mh_d(const KArgs &a, hipStream_t st, size_t lds) {
     }
   }
   if (a.rng == PBH_RNG_PHILOX_FP32) return hipErrorInvalidValue;   // pair kernel only
-  // the expression target: its own instances (pbh_expr.hip), never the
-  // generic form below, whose density switch does not hold the interpreter
-  // (a program with loop regions: the kernels of pbh_expr_data.hip)
-  if (a.target == PBH_TARGET_EXPR)
-    return a.edata ? launch_mh_expr_data(a, st) : launch_mh_expr(a, st);
+  // the expression target: its own instances (pbh_expr.hip, and for a program
+  // with loop regions pbh_expr_data.hip), never the generic form below, whose
+  // density switch does not hold the interpreter
+  if (a.target == PBH_TARGET_EXPR) return launch_mh_expr(a, st);
   // Specialised forms: the cfg2 diagonal Gaussian with the callable Gaussian
   // delta at every d; the other example forms at the small d they use.
   if (a.target == PBH_TARGET_DIAG_GAUSS && a.prop == PBH_PROP_GAUSS) {

@@ -11,6 +11,7 @@ import oracle.mh
 import probayes_amd as pb
 from probayes_amd import expr
 from probayes_amd.engine import Engine, eval_expr
+import expr_programs
 from expr_examples import EXPR_WORKLOADS, banana_lp
 
 pytestmark = pytest.mark.gpu
@@ -31,12 +32,7 @@ def _rel_err(a, b, floor=np.finfo(float).tiny):
 # ---------------------------------------------------------------------------
 # 1. pbh_eval_expr against expr.evaluate
 # ---------------------------------------------------------------------------
-def _arith(**kw):
-  """+ - * /, square, sqrt, neg, abs, max, min: IEEE operations only."""
-  x, y, z = kw['x'], kw['y'], kw['z']
-  r = np.sqrt(abs(x) + y * y + 1.5) / (np.square(z) + 0.25)
-  m = np.maximum(x - y, z * 0.5) + np.minimum(-x, y / 3.)
-  return -(r * m - x / (abs(z) + 2.)) + r
+_arith = expr_programs.arith
 
 
 def _every_opcode():
@@ -132,20 +128,12 @@ def test_eval_expr_matches_numpy_interpreter(which, n):
 
 def test_set_model_refuses_bad_programs():
   from probayes_amd._lib import PbhError
-  good = expr.trace_expr(_arith, ['x', 'y', 'z'])
+  good, bad = expr_programs.scalar_cases()
   pts = _eval_points(4)
-  bad = good['code'].copy()
-  bad[0] = expr.encode(expr.ADD, (expr.VAR, 3), (expr.VAR, 0))     # variable 3 of 3
-  with pytest.raises(PbhError):
-    eval_expr(bad, good['consts'], good['depth'], pts)
-  bad[0] = expr.encode(expr.NEG, (expr.SLOT, 5))                   # unwritten slot
-  with pytest.raises(PbhError):
-    eval_expr(bad, good['consts'], good['depth'], pts)
-  bad[0] = expr.N_OPS                                              # unknown opcode
-  with pytest.raises(PbhError):
-    eval_expr(bad, good['consts'], good['depth'], pts)
-  with pytest.raises(PbhError):
-    eval_expr(good['code'], good['consts'][:1], good['depth'], pts)
+  assert len(bad) == 4
+  for p in bad:
+    with pytest.raises(PbhError):
+      eval_expr(p.code, p.consts, p.depth, pts)
 
 
 # ---------------------------------------------------------------------------

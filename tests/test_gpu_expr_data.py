@@ -11,6 +11,7 @@ import probayes_amd as pb
 from probayes_amd import expr
 from probayes_amd._lib import PbhError
 from probayes_amd.engine import Engine, eval_expr
+import expr_programs
 from expr_data_examples import DATA_WORKLOADS
 
 pytestmark = pytest.mark.gpu
@@ -108,36 +109,18 @@ def test_eval_expr_data_matches_numpy_interpreter(which, n, points):
 # 2. bad programs are refused before any launch
 # ---------------------------------------------------------------------------
 def test_set_model_refuses_bad_data_programs(monkeypatch):
-  E, V, A, S, B = expr.encode, expr.VAR, expr.ACC, expr.SLOT, expr.BODY_BASE
-  data = np.ones((2, 9))
+  good, bad = expr_programs.data_cases()
   pts = np.zeros((4, 1))
-  loop = lambda n: E(expr.LOOP, (S, n))
-  total = E(expr.SUM, (A, 0))
-  body = [E(expr.MUL, (V, B + 0), (V, 0))]
-  good = [loop(1)] + body + [total]
-  assert np.array_equal(eval_expr(good, [], 0, pts + 2., data=data), np.full(4, 18.))
-  bad = [
-      [loop(3), loop(1)] + body + [total, total],                        # nested
-      [loop(1), E(expr.MUL, (V, B + 2), (V, 0)), total],                 # column 2 of 2
-      [loop(1), E(expr.MUL, (V, B + 0), (S, B + 0)), total],             # unwritten temporary
-      [loop(1), E(expr.MUL, (V, B + 0), (V, 0), dst=4, store=True), total],
-      [loop(1), E(expr.NEG, (A, 0)), total],                             # acc, first word
-      [loop(2)] + body + [total],                                        # no SUM at the end
-      [loop(1)] + body,                                                  # past the end
-      body + [total],                                                    # SUM alone
-      [loop(1), E(expr.MUL, (V, B + 0), (S, 0)), total],                 # unwritten slot
-  ]
-  for code in bad:
+  assert np.array_equal(eval_expr(good.code, good.consts, good.depth, pts + 2., data=good.data),
+                        np.full(4, 18.))
+  assert len(bad) == 11
+  for p in bad:
     with pytest.raises(PbhError):
-      eval_expr(code, [], 1, pts, data=data)
-  with pytest.raises(PbhError):
-    eval_expr(good, [], 0, pts, data=np.ones((9, 4)))                    # nine columns
-  with pytest.raises(PbhError):
-    eval_expr(good, [], 0, pts, data=np.ones((1, expr.MAX_OBS + 1)))
+      eval_expr(p.code, p.consts, p.depth, pts, data=p.data)
   # through pbh_set_model: the engine's own check (make_spec's is bypassed)
-  spec = pb.make_spec(1, {'kind': 'expr', 'code': good, 'consts': [], 'depth': 0,
-                          'data': data}, {'kind': 'gauss', 'scale': 1.}, pscale='log')
-  spec['target']['code'] = np.array(bad[1], np.int32)
+  spec = pb.make_spec(1, {'kind': 'expr', 'code': good.code, 'consts': [], 'depth': 0,
+                          'data': good.data}, {'kind': 'gauss', 'scale': 1.}, pscale='log')
+  spec['target']['code'] = np.array(bad[1].code, np.int32)
   import probayes_amd.engine as engine_mod
   monkeypatch.setattr(engine_mod, 'normalize_spec', lambda s: s)
   with pytest.raises(PbhError):
