@@ -287,8 +287,8 @@ int pbh_get_checkpoint(pbh_engine *eng, double *x, double *lp, int64_t *step,
 int pbh_restore(pbh_engine *eng, const double *x, const double *lp,
                 int64_t step, int32_t has_pred, const uint32_t *xo);
 /* The device legacy streams' state for a checkpoint (pbh_legacy_seed):
- * key [words][N] with words per chain from pbh_legacy_state_words (624 in
- * place, 1248 double-buffered, 640 for the default chunked layout: the
+ * key [words][N] with words per chain from pbh_legacy_state_words (1248
+ * double-buffered, 640 for the default chunked layout: the
  * current block, moved into buffer 0 by the get; the words are the device
  * layout, opaque to the caller and valid only for an engine seeded with the
  * same layout), the read position pos [N]

@@ -54,11 +54,9 @@ struct pbh_engine {
   bool xo_seeded = false;
   // legacy NumPy RandomState per chain (pbh_legacy_seed)
   uint32_t *mt_key = nullptr;
-  int mt_mode = 0;             // mt_key layout: 0 [624][n], 1 [2][624][n], 2 Mt4's
-                               // [4][20][n][32] (four chunked blocks)
-  bool legacy_db = true;       // PBH_LEGACY_DB=0: the in-place state
-  bool legacy_k4 = true;       // PBH_LEGACY_K4=0: the round-3 double-buffered state
-  bool legacy_win = true;      // PBH_LEGACY_WIN=0: HBM-direct consumption (Mt2)
+  bool mt_k4 = true;           // mt_key layout: Mt4's [16][20][n][32] (chunked blocks),
+                               // or the double-buffered [2][624][n] (Mt3)
+  bool legacy_k4 = true;       // PBH_LEGACY_K4=0: the double-buffered state at any chain count
   bool legacy_fused = true;    // PBH_LEGACY_FUSED=0: pbh_legacy_run as generation + run
   bool legacy_wp = true;       // PBH_LEGACY_WP=0: the chain-per-lane generator for MH streams
   bool legacy_ahead = true;    // PBH_LEGACY_AHEAD=0: no twist-ahead pass before fused launches
@@ -102,7 +100,6 @@ struct pbh_engine {
   bool pair_full = true;     // PBH_PAIR_FULL=0: no steady-state pair kernel
   int ess_fft = 2;           // PBH_ESS_FFT=1: the 4 096-point form only, 0: direct sums
   bool iid_full = true;      // PBH_IID_FULL=0: no steady-state iid kernel
-  bool iid_pair = false;     // PBH_IID_PAIR=1: the steady-state iid kernel on lane pairs (measured slower)
   int fair = 11;             // PBH_FAIR=k: wave priorities alternate every 2^k x 10 ns (0: off)
   int pair_wg = 512;         // PBH_PAIR_WG=256: FULL pair kernel in 4-wave workgroups
                              // (512: one table copy per CU, 20-step launches ~5 % faster)
@@ -173,13 +170,13 @@ struct pbh_engine {
 
 namespace {
 
-// words of legacy state per chain in each layout (pbh_engine.mt_mode)
 constexpr double pbh_mt_block_words() { return 624.0; }
-// (mode 2: pbh_mt.h kK4 = 16 buffers of 20 chunks of 32 words)
-int64_t mt_words(int mode) { return mode == 2 ? 16 * 20 * 32 : mode == 1 ? 2 * 624 : 624; }
+// words of legacy state per chain in each layout (pbh_engine.mt_k4): Mt4's
+// kK4 = 16 buffers of 20 chunks of 32 words (pbh_mt.h), or two blocks
+int64_t mt_words(bool k4) { return k4 ? 16 * 20 * 32 : 2 * 624; }
 // words per chain of the checkpoint form (pbh_get/set_legacy_state): Mt4's
 // current block alone, moved into buffer 0 (launch_legacy_normalize)
-int64_t mt_state_words(int mode) { return mode == 2 ? 20 * 32 : mt_words(mode); }
+int64_t mt_state_words(bool k4) { return k4 ? 20 * 32 : mt_words(k4); }
 
 thread_local std::string g_err;
 
@@ -665,14 +662,11 @@ int pbh_create(int device, pbh_engine **out) {
     e->srv_idle_ms = std::max<int64_t>(1, std::min<int64_t>(10000, std::atoll(si)));
   if (const char *ef = std::getenv("PBH_ESS_FFT")) e->ess_fft = std::atoi(ef);
   if (const char *fi = std::getenv("PBH_IID_FULL")) e->iid_full = std::atoi(fi) != 0;
-  if (const char *fp = std::getenv("PBH_IID_PAIR")) e->iid_pair = std::atoi(fp) != 0;
   if (const char *fa = std::getenv("PBH_FAIR")) e->fair = std::min(20, std::max(0, std::atoi(fa)));
   if (const char *wg = std::getenv("PBH_PAIR_WG")) e->pair_wg = std::atoi(wg);
   if (const char *fs = std::getenv("PBH_FAIR_SHORT"))
     e->fair_short = std::min(20, std::max(0, std::atoi(fs)));
   if (const char *fr = std::getenv("PBH_FAIR_REL")) e->fair_rel = std::atoi(fr) != 0;
-  if (const char *ld = std::getenv("PBH_LEGACY_DB")) e->legacy_db = std::atoi(ld) != 0;
-  if (const char *lw = std::getenv("PBH_LEGACY_WIN")) e->legacy_win = std::atoi(lw) != 0;
   if (const char *lk = std::getenv("PBH_LEGACY_K4")) e->legacy_k4 = std::atoi(lk) != 0;
   if (const char *lf = std::getenv("PBH_LEGACY_FUSED")) e->legacy_fused = std::atoi(lf) != 0;
   if (const char *lp = std::getenv("PBH_LEGACY_WP")) e->legacy_wp = std::atoi(lp) != 0;
@@ -1261,12 +1255,10 @@ int pbh_legacy_seed(pbh_engine *e, const uint32_t *seeds) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   // the state layout is fixed at seeding
   // (Mt4's resources take 32-bit byte offsets: its state must span < 2^32 B)
-  e->mt_mode = !e->legacy_db ? 0
-               : (e->legacy_k4 && e->legacy_win && mt_words(2) * 4 * n < (int64_t(1) << 32)) ? 2
-                                                                                          : 1;
+  e->mt_k4 = e->legacy_k4 && mt_words(true) * 4 * n < (int64_t(1) << 32);
   e->mt_stale = false;
   e->mt_odd = false;
-  int rc = dalloc(e->mt_key, (size_t)mt_words(e->mt_mode) * n);
+  int rc = dalloc(e->mt_key, (size_t)mt_words(e->mt_k4) * n);
   if (!rc) rc = dalloc(e->mt_pos, n);
   if (!rc) rc = dalloc(e->mt_has, n);
   if (!rc) rc = dalloc(e->mt_gauss, n);
@@ -1277,7 +1269,7 @@ int pbh_legacy_seed(pbh_engine *e, const uint32_t *seeds) {
   hipError_t err = hipMemcpy(dseeds, seeds, n * sizeof(uint32_t), hipMemcpyHostToDevice);
   if (err == hipSuccess)
     err = pbh::launch_legacy_seed(e->mt_key, e->mt_pos, e->mt_gauss, e->mt_has,
-                                  dseeds, n, e->mt_mode, e->stream);
+                                  dseeds, n, e->mt_k4, e->stream);
   if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
   dfree(dseeds);
   if (err != hipSuccess)
@@ -1303,6 +1295,69 @@ int pbh_reserve_replay(pbh_engine *e, int64_t n_steps) {
     e->rep_steps = 0;
   }
   return rc;
+}
+
+// ---- the set-up shared by pbh_legacy_replay and pbh_legacy_run ----
+
+// Launches of at most kLegacyLaunchSteps steps: the generator counts a
+// launch's stream quads per chain in 32-bit ints (Mt4's head index), and a
+// step takes a bounded-in-expectation but unbounded number of words (polar
+// rejections, randint masks), so the launch length is what is bounded:
+// 2^20 steps x R <= 33 draws x ~3 words per draw is ~2^27 quads << 2^31.
+// The state (position, block, pending gauss) persists between launches, so
+// the split is invisible in the stream.
+static constexpr int64_t kLegacyLaunchSteps = int64_t(1) << 20;
+
+// legacy_log_table on the device (Mt4's polar log), uploaded once
+static int legacy_lgtab(pbh_engine *e) {
+  if (e->lgtab) return PBH_OK;
+  std::vector<double> lt(pbh::kLegLogDoubles);
+  pbh::legacy_log_table(lt.data());
+  if (const int rc = dalloc(e->lgtab, lt.size())) return rc;
+  HIP_TRY(hipMemcpy(e->lgtab, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
+  return PBH_OK;
+}
+
+// the generator's state and the draw form of the engine's sampler (R draws
+// per step); the caller sets what its launches add (order, out, the steps)
+static pbh::LegacyArgs legacy_args(const pbh_engine *e, int32_t R) {
+  pbh::LegacyArgs a{};
+  a.key = e->mt_key; a.pos = e->mt_pos; a.gauss = e->mt_gauss; a.has_gauss = e->mt_has;
+  a.n = e->n; a.d = e->d; a.R = R; a.gibbs = e->has_gibbs ? 1 : 0;
+  a.normal = (!e->has_gibbs && e->k.prop == PBH_PROP_GAUSS) ? 1 : 0;
+  a.vardelta = (!e->has_gibbs && e->k.prop == PBH_PROP_VARDELTA) ? 1 : 0;
+  a.k4 = e->mt_k4 ? 1 : 0;
+  a.lgtab = e->lgtab;
+  return a;
+}
+
+// Twist-ahead (legacy_ahead_kernel, PBH_LEGACY_AHEAD=0 off) for the
+// chain-per-lane Mt4 generators: each launch's blocks are twisted before it
+// by one wavefront per chain, so the launch only consumes (a chain that needs
+// more twists in its own kernel, as without the pre-pass).  ahead_words: the
+// words m steps take.  Doubles per step (mean, variance): normal -- d/2 pairs
+// at 4/pi attempts of two doubles (attempt-count variance 0.348 per pair) +
+// the threshold, with an 8-sigma margin; raw -- d + 1; per-variable -- at
+// least that (randint's masked rejections beyond it twist in the generator);
+// Gibbs -- at most R.  (The variance is formed before it meets m: against
+// sqrt(m * 4 * 0.348 * d / 2) the value can differ in the last bit, the block
+// count and the 14-block test below in no case for m <= 2^20, d <= 32.)
+static double ahead_words(const pbh::LegacyArgs &a, int64_t m) {
+  const double mm = (double)m, dd = (double)a.d;
+  if (a.gibbs) return 2.0 * (mm * a.R + 2.0);
+  const double dmean = a.normal ? 4.0 * dd / 3.14159265358979 + 1.0 : dd + 1.0;
+  const double dvar = a.normal ? 4.0 * 0.3480 * dd / 2.0 : 0.0;
+  return 2.0 * (mm * dmean + 8.0 * std::sqrt(mm * dvar) + 2.0);
+}
+// the launch length, at most cap, that 14 whole blocks after the current
+// one's (up to 624) words hold
+static int64_t ahead_fit(const pbh::LegacyArgs &a, int64_t cap) {
+  while (cap > 1 && ahead_words(a, cap) > 14.0 * pbh_mt_block_words()) cap = cap * 7 / 8;
+  return cap;
+}
+// blocks to twist ahead of a launch of m steps
+static int32_t ahead_want(const pbh::LegacyArgs &a, int64_t m) {
+  return std::min<int32_t>(15, 1 + (int32_t)std::ceil(ahead_words(a, m) / pbh_mt_block_words()));
 }
 
 int pbh_legacy_replay(pbh_engine *e, int64_t n_steps) {
@@ -1332,64 +1387,26 @@ int pbh_legacy_replay(pbh_engine *e, int64_t n_steps) {
     if (!rc) HIP_TRY(hipMemcpy(e->mt_order, e->draw_order.data(),
                                e->d * sizeof(int32_t), hipMemcpyHostToDevice));
   }
+  if (!rc) rc = legacy_lgtab(e);
   if (rc) return rc;
-  pbh::LegacyArgs a{};
-  a.key = e->mt_key; a.pos = e->mt_pos; a.gauss = e->mt_gauss;
-  a.has_gauss = e->mt_has; a.order = e->mt_order; a.out = e->rep;
-  a.n = n; a.n_steps = n_steps; a.step0 = e->g;
-  a.d = e->d; a.R = R; a.gibbs = e->has_gibbs ? 1 : 0;
-  a.normal = (!e->has_gibbs && e->k.prop == PBH_PROP_GAUSS) ? 1 : 0;
-  a.vardelta = (!e->has_gibbs && e->k.prop == PBH_PROP_VARDELTA) ? 1 : 0;
-  a.db = e->mt_mode;
-  a.win = e->legacy_win ? 1 : 0;
+  pbh::LegacyArgs a = legacy_args(e, R);
+  a.order = e->mt_order;
   a.vmode = e->k.vmode;
   a.vdelta = e->k.pdel;
   a.wp = (e->legacy_wp && !e->mt_odd) ? 1 : 0;
   if (a.vardelta) e->mt_odd = true;   // randint may leave odd positions
-  if (!e->lgtab) {
-    std::vector<double> lt(pbh::kLegLogDoubles);
-    pbh::legacy_log_table(lt.data());
-    rc = dalloc(e->lgtab, lt.size());
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(e->lgtab, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  a.lgtab = e->lgtab;
-  // Launches of at most kLegacyLaunchSteps steps: the generator counts a
-  // launch's stream quads per chain in 32-bit ints (Mt4's head index), and a
-  // step takes a bounded-in-expectation but unbounded number of words (polar
-  // rejections, randint masks), so the launch length is what is bounded:
-  // 2^20 steps x R <= 33 draws x ~3 words per draw is ~2^27 quads << 2^31.
-  // The state (position, block, pending gauss) persists between launches, so
-  // the split is invisible in the stream.
-  constexpr int64_t kLegacyLaunchSteps = int64_t(1) << 20;
-  // the twist-ahead pass (as pbh_legacy_run) for the chain-per-lane Mt4
-  // generator -- Gibbs rows, per-variable deltas, raw draws, odd positions;
-  // the word-parallel generator twists in its own LDS.  Words per step: Gibbs
-  // at most 2R, per-variable at least 2 per draw (randint's masked
-  // rejections beyond that twist in the generator), raw 2(d + 1), normal the
-  // polar method's mean + 8 sigma
+  // the twist-ahead pass for the chain-per-lane Mt4 generator -- Gibbs rows,
+  // per-variable deltas, raw draws, odd positions; the word-parallel
+  // generator twists in its own LDS
   const bool wp_path = a.wp && !a.gibbs && !a.vardelta;
-  const bool ahead = e->legacy_ahead && e->mt_mode == 2 && !wp_path;
-  const double dd = (double)e->d;
-  auto ahead_words = [&](int64_t m) {
-    const double mm = (double)m;
-    if (a.gibbs) return 2.0 * (mm * R + 2.0);
-    if (a.vardelta || !a.normal) return 2.0 * (mm * (dd + 1.0) + 2.0);
-    return 2.0 * (mm * (4.0 * dd / 3.14159265358979 + 1.0) +
-                  8.0 * std::sqrt(mm * 4.0 * 0.3480 * dd / 2.0) + 2.0);
-  };
-  int64_t k_fit = kLegacyLaunchSteps;
-  if (ahead) {
-    k_fit = std::min<int64_t>(n_steps, kLegacyLaunchSteps);
-    while (k_fit > 1 && ahead_words(k_fit) > 14.0 * pbh_mt_block_words()) k_fit = k_fit * 7 / 8;
-  }
+  const bool ahead = e->legacy_ahead && e->mt_k4 && !wp_path;
+  const int64_t k_fit =
+      ahead ? ahead_fit(a, std::min(n_steps, kLegacyLaunchSteps)) : kLegacyLaunchSteps;
   hipError_t err = hipSuccess;
   for (int64_t done = 0; done < n_steps && err == hipSuccess;) {
     const int64_t k = std::min(std::min(n_steps - done, kLegacyLaunchSteps), k_fit);
     if (ahead) {
-      const int32_t want = std::min<int32_t>(
-          15, 1 + (int32_t)std::ceil(ahead_words(k) / pbh_mt_block_words()));
-      err = pbh::launch_legacy_ahead(e->mt_key, e->mt_pos, n, want, e->stream);
+      err = pbh::launch_legacy_ahead(e->mt_key, e->mt_pos, n, ahead_want(a, k), e->stream);
       if (err != hipSuccess) break;
     }
     a.out = e->rep + (size_t)done * R * n;
@@ -1580,7 +1597,6 @@ static void run_args(pbh_engine *e, KArgs &k, size_t &lds) {
   k.gmm_full = e->gmm_full ? 1 : 0;
   k.pair_full = e->pair_full ? 1 : 0;
   k.iid_full = e->iid_full ? 1 : 0;
-  k.iid_pair = e->iid_pair ? 1 : 0;
   k.fair = e->fair;
   k.pair_wg = e->pair_wg;
   k.gq = e->gq;
@@ -1755,7 +1771,7 @@ int pbh_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
 // legacy_mh_kernel): the draws never pass through HBM.  Same chains, trace
 // and legacy state as pbh_legacy_replay + pbh_run chunk by chunk, which is
 // what runs for the forms the fused kernel does not cover (Gibbs, per-
-// variable deltas, a permuted draw order, the pre-Mt4 state layouts, a d
+// variable deltas, a permuted draw order, the double-buffered state, a d
 // without an instantiation) and with PBH_LEGACY_FUSED=0.  The stream buffer
 // is not written: afterwards no replay rows are held (pbh_get_replay).
 int pbh_legacy_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
@@ -1780,21 +1796,8 @@ int pbh_legacy_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
   KArgs k;
   size_t lds = 0;
   run_args(e, k, lds);
-  if (!e->lgtab) {
-    std::vector<double> lt(pbh::kLegLogDoubles);
-    pbh::legacy_log_table(lt.data());
-    if (const int rc = dalloc(e->lgtab, lt.size())) return rc;
-    HIP_TRY(hipMemcpy(e->lgtab, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  pbh::LegacyArgs la{};
-  la.key = e->mt_key; la.pos = e->mt_pos; la.gauss = e->mt_gauss;
-  la.has_gauss = e->mt_has; la.order = nullptr; la.out = nullptr;
-  la.n = e->n; la.d = e->d; la.R = R; la.gibbs = e->has_gibbs ? 1 : 0;
-  la.normal = (!e->has_gibbs && e->k.prop == PBH_PROP_GAUSS) ? 1 : 0;
-  la.vardelta = (!e->has_gibbs && e->k.prop == PBH_PROP_VARDELTA) ? 1 : 0;
-  la.db = e->mt_mode;
-  la.win = e->legacy_win ? 1 : 0;
-  la.lgtab = e->lgtab;
+  if (const int rc = legacy_lgtab(e)) return rc;
+  pbh::LegacyArgs la = legacy_args(e, R);
   bool ident = true;
   for (int j = 0; j < (int)e->draw_order.size(); ++j) ident = ident && e->draw_order[j] == j;
   // the fused kernel has no instance for the expression target (its generic
@@ -1835,36 +1838,15 @@ int pbh_legacy_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
     lev.start = e->ev0;
     lev.stop = nullptr;
   }
-  // launches of at most 2^20 steps, as pbh_legacy_replay (Mt4's 32-bit head)
-  constexpr int64_t kLegacyLaunchSteps = int64_t(1) << 20;
-  // twist-ahead (legacy_ahead_kernel, PBH_LEGACY_AHEAD=0 off): each launch's
-  // blocks are twisted before it by one wavefront per chain, so the fused
-  // kernel only consumes; a launch is at most what 15 blocks ahead hold with
-  // an 8-sigma margin on the polar method's attempts (a chain that needs more
-  // twists in the fused kernel, as without the pre-pass)
-  const bool ahead = e->legacy_ahead && e->mt_mode == 2 && !e->mt_odd;
-  const double dd = (double)e->d;
-  // doubles per step (mean, variance): normal -- d/2 pairs at 4/pi attempts
-  // of two doubles (attempt-count variance 0.348 per pair) + the threshold;
-  // raw -- d + 1
-  const double dmean = la.normal ? 4.0 * dd / 3.14159265358979 + 1.0 : dd + 1.0;
-  const double dvar = la.normal ? 4.0 * 0.3480 * dd / 2.0 : 0.0;
-  auto ahead_words = [&](int64_t m) {   // words of m steps, 8 sigma
-    return 2.0 * ((double)m * dmean + 8.0 * std::sqrt((double)m * dvar) + 2.0);
-  };
-  int64_t m_fit = spl;
-  if (ahead) {   // 14 whole blocks after the current one's (up to 624) words
-    while (m_fit > 1 && ahead_words(m_fit) > 14.0 * pbh_mt_block_words()) m_fit = m_fit * 7 / 8;
-  }
+  // the twist-ahead pass: the fused kernel then only consumes
+  const bool ahead = e->legacy_ahead && e->mt_k4 && !e->mt_odd;
+  const int64_t m_fit = ahead ? ahead_fit(la, spl) : spl;
   int64_t launches = 0;
   for (int64_t done = 0; done < n_steps;) {
-    int64_t m = std::min(std::min(spl, kLegacyLaunchSteps), n_steps - done);
+    const int64_t m = std::min(std::min(std::min(spl, kLegacyLaunchSteps), n_steps - done), m_fit);
     if (ahead) {
-      m = std::min(m, m_fit);
-      const int32_t want = std::min<int32_t>(
-          15, 1 + (int32_t)std::ceil(ahead_words(m) / pbh_mt_block_words()));
-      const hipError_t ea = pbh::launch_legacy_ahead(e->mt_key, e->mt_pos, e->n, want,
-                                                     e->stream);
+      const hipError_t ea = pbh::launch_legacy_ahead(e->mt_key, e->mt_pos, e->n,
+                                                     ahead_want(la, m), e->stream);
       if (ea != hipSuccess) {
         lev = {};
         return fail(PBH_ERR_HIP, "pbh_legacy_run (twist-ahead): %s", hipGetErrorString(ea));
@@ -1939,7 +1921,7 @@ int pbh_legacy_draws(pbh_engine *e, int64_t n_steps, int64_t step0, int32_t kind
   if (e->mt_stale)
     return fail(PBH_ERR_STATE, "pbh_restore ran after pbh_legacy_seed: set the "
                 "checkpoint's legacy state (pbh_set_legacy_state) first");
-  if (e->mt_mode != 2) return fail(PBH_ERR_UNSUPPORTED, "pbh_legacy_draws needs the Mt4 state");
+  if (!e->mt_k4) return fail(PBH_ERR_UNSUPPORTED, "pbh_legacy_draws needs the Mt4 state");
   if (kind != PBH_DRAWS_GAUSS && kind != PBH_DRAWS_LINREG)
     return fail(PBH_ERR_ARG, "bad draws kind %d", kind);
   if (n_steps < 0 || step0 < 0) return fail(PBH_ERR_ARG, "n_steps, step0 must be >= 0");
@@ -1953,7 +1935,7 @@ int pbh_legacy_draws(pbh_engine *e, int64_t n_steps, int64_t step0, int32_t kind
   pbh::LegacyArgs a{};
   a.key = e->mt_key; a.pos = e->mt_pos; a.gauss = e->mt_gauss; a.has_gauss = e->mt_has;
   a.out = dout; a.n = n; a.n_steps = n_steps; a.step0 = step0; a.d = 1; a.R = 1;
-  a.db = e->mt_mode;
+  a.k4 = 1;
   hipError_t err = pbh::launch_legacy_draws(a, kind, param, e->stream);
   if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
   if (err == hipSuccess)
@@ -2219,7 +2201,7 @@ int pbh_set_chain_logs(pbh_engine *e, const double *lx) {
 
 int pbh_legacy_state_words(pbh_engine *e, int64_t *words) {
   if (check_ptr(e, "engine") || check_ptr(words, "words")) return PBH_ERR_ARG;
-  *words = e->mt_key ? mt_state_words(e->mt_mode) : 0;
+  *words = e->mt_key ? mt_state_words(e->mt_k4) : 0;
   return PBH_OK;
 }
 
@@ -2232,9 +2214,9 @@ int pbh_get_legacy_state(pbh_engine *e, uint32_t *key, int32_t *pos,
   if (!e->mt_key) return fail(PBH_ERR_STATE, "no legacy streams (pbh_legacy_seed)");
   if (e->mt_stale) return fail(PBH_ERR_STATE, "legacy state stale after pbh_restore");
   const int64_t n = e->n;
-  const size_t kw = (size_t)mt_state_words(e->mt_mode) * n;
+  const size_t kw = (size_t)mt_state_words(e->mt_k4) * n;
   HIP_TRY(hipSetDevice(e->device));
-  if (e->mt_mode == 2)   // the current blocks into buffer 0: the key's prefix
+  if (e->mt_k4)   // the current blocks into buffer 0: the key's prefix
     HIP_TRY(pbh::launch_legacy_normalize(e->mt_key, e->mt_pos, n, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   HIP_TRY(hipMemcpy(key, e->mt_key, kw * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -2252,11 +2234,11 @@ int pbh_set_legacy_state(pbh_engine *e, const uint32_t *key, const int32_t *pos,
   SRV_STOP(e);
   if (!e->mt_key) return fail(PBH_ERR_STATE, "pbh_legacy_seed first (the layout)");
   const int64_t n = e->n;
-  const size_t kw = (size_t)mt_state_words(e->mt_mode) * n;
+  const size_t kw = (size_t)mt_state_words(e->mt_k4) * n;
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
   HIP_TRY(hipMemcpy(e->mt_key, key, kw * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (e->mt_mode == 2) {   // the checkpoint form: the block in buffer 0
+  if (e->mt_k4) {   // the checkpoint form: the block in buffer 0
     std::vector<int32_t> p0(pos, pos + n);
     for (auto &v : p0) v &= 0xFFFF;
     HIP_TRY(hipMemcpy(e->mt_pos, p0.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -2938,12 +2920,6 @@ int pbh_linreg_gibbs(int device, int64_t n_obs, const double *x_obs,
   h.stats[3] = (double)cxy; h.stats[4] = (double)cyy;
   h.n_obs = n_obs; h.n = n_chains; h.chain_offset = chain_offset;
   h.n_steps = n_steps; h.step0 = step0; h.seed = seed; h.mode = rng_mode;
-  {
-    // the lane-pair kernel is measured slower (1.60 vs 1.22 ms at 65 536
-    // chains x 1 000 steps); PBH_LINREG_PAIR=1 selects it for A/B runs
-    const char *p_env = std::getenv("PBH_LINREG_PAIR");
-    h.pair = p_env && p_env[0] == '1';
-  }
   if (kernel_ms) *kernel_ms = 0.;
   HIP_TRY(hipSetDevice(device));
   const int64_t T = n_steps, N = n_chains;

@@ -128,7 +128,6 @@ struct KArgs {
   int32_t gmm_full;    // the quad kernel's steady-state form is allowed
   int32_t pair_full;   // the lane-pair kernel's steady-state form is allowed
   int32_t iid_full;    // cfg1's steady-state iid-Normal form is allowed
-  int32_t iid_pair;    // ... on lane pairs (mh_iid_pair_kernel)
   int32_t fair;        // alternate the SIMD's wave priorities every 2^fair real-time ticks (0: off)
   int32_t pair_wg;     // FULL pair kernel's workgroup size (256 or 512)
   int32_t fair_rel;    // FULL pair kernel: the alternation clock starts at the wave's loop entry
@@ -251,22 +250,21 @@ constexpr int kLegLogN = 129, kLegLogInv = 2 * kLegLogN, kLegLogDoubles = 3 * kL
 void legacy_log_table(double *out);
 // Legacy (NumPy RandomState) stream generation (pbh_legacy.hip).
 struct LegacyArgs {
-  uint32_t *key;        // MT19937 words [624][n]
-  int32_t *pos;         // next word per chain [n]
+  uint32_t *key;        // MT19937 words (layout: k4)
+  int32_t *pos;         // packed position per chain [n]
   double *gauss;        // cached polar deviate [n]
   int32_t *has_gauss;   // [n]
   const int32_t *order; // draw j -> replay row order[j] (MH)
   double *out;          // replay rows [n_steps][R][n]
   int64_t n, n_steps, step0;
   int32_t d, R, gibbs, normal;
-  int32_t db;           // 1: double-buffered state [2][624][n] (legacy_gen_db);
-                        // 2: four chunked blocks [4][20][n][32 words] (Mt4)
-  int32_t win;          // with db: consume through the LDS window (Mt3)
+  int32_t k4;           // 1: chunked blocks [16][20][n][32 words] (Mt4);
+                        // 0: double-buffered state [2][624][n] (Mt3)
   int32_t vardelta;     // VARDELTA: per-dim modes vmode, steps vdelta [d]
   uint64_t vmode;
   const double *vdelta;
   const double *lgtab;  // legacy_log_table (Mt4's polar log)
-  int32_t wp;           // with db == 2: the word-parallel generator for MH
+  int32_t wp;           // with k4: the word-parallel generator for MH
                         // streams of doubles (every position even)
   double *thr;          // the fused kernel: each step's threshold [n_steps][n]
                         // (nullptr: not kept)
@@ -277,7 +275,7 @@ hipError_t launch_legacy_draws(const LegacyArgs &a, int32_t kind, double param,
                                hipStream_t s);
 hipError_t launch_legacy_seed(uint32_t *key, int32_t *pos, double *gauss,
                               int32_t *has_gauss, const uint32_t *seeds,
-                              int64_t n, int32_t db, hipStream_t s);
+                              int64_t n, bool k4, hipStream_t s);
 hipError_t launch_legacy_gen(const LegacyArgs &a, hipStream_t s);
 // Mt4 state: twist every chain's buffers ahead until `want` (<= 15) blocks
 // follow its current one (legacy_ahead_kernel)
@@ -317,7 +315,6 @@ struct LinregArgs {
   int64_t n, chain_offset, n_steps, step0;
   uint64_t seed;
   int32_t mode;
-  int32_t pair;   // PHILOX: one chain per lane pair (linreg_pair_kernel)
 };
 int64_t linreg_max_obs();
 hipError_t launch_linreg_gibbs(const LinregArgs &a, hipStream_t s);

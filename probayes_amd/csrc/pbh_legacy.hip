@@ -9,10 +9,10 @@
 // the draws in the replay layout [T][R][N] the REPLAY kernels read -- so a
 // full-width reference-identical run needs no host stream generation.
 //
-// State per chain: key[624] in [624][N] (word-major, so lanes of a wave
-// touch neighbouring words while their positions agree), pos, the cached
-// gauss and its flag.  Lanes drift apart (the polar rejection consumes a
-// variable number of words); correctness does not depend on it.
+// State per chain: the MT19937 blocks (Mt4's chunked buffers, or Mt3's two
+// blocks once Mt4's state would span 2^32 bytes), a packed position, the
+// cached gauss and its flag.  Lanes drift apart (the polar rejection consumes
+// a variable number of words); correctness does not depend on it.
 // Per step the order is the reference's: MH draws d normals (callable
 // Gaussian Delta) or d raw doubles (tuple / list delta), then one double for
 // the threshold; CondCov Gibbs draws one double per updated coordinate of
@@ -31,122 +31,32 @@ namespace {
 
 constexpr int kBlockLegacy = 256;   // threads per workgroup of the generators
 
-__global__ __launch_bounds__(256) void mt_seed_kernel(uint32_t *key, int32_t *pos,
-                                                      double *gauss, int32_t *has_gauss,
-                                                      const uint32_t *seeds, int64_t n) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n) return;
-  uint32_t s = seeds[c];
-  // mt19937_seed (init_genrand)
-  for (int i = 0; i < kN; ++i) {
-    key[(int64_t)i * n + c] = s;
-    s = 1812433253u * (s ^ (s >> 30)) + (uint32_t)(i + 1);
-  }
-  pos[c] = kN;
-  gauss[c] = 0.0;
-  has_gauss[c] = 0;
-}
-
-struct Mt {
-  static constexpr bool kLockstep = false;
-  static constexpr bool kPeek = false;
-  static constexpr bool kPeek4 = false;
-  static constexpr bool kLogTab = false;
-  uint32_t *key;
-  int64_t n, c;
-  int pos;
-
-  __device__ __forceinline__ uint32_t &k(int i) { return key[(int64_t)i * n + c]; }
-
-  // mt19937_gen in the reference order (later words read updated ones),
-  // in chunks of kB words whose loads are all issued before the chunk's
-  // stores: a chunk reads k[i+1 .. i+kB] (old values, read before they are
-  // overwritten, as in the sequential loop) and k[j] with j = i + 397 (not yet
-  // written) or j = i - 227 (written by an earlier chunk since kB <= 227), so
-  // the result is the sequential one while kB loads are in flight instead of
-  // one.  The chunk grid splits at 227 = N - M (where j wraps) and at 623.
-  // 98 -> 29 ms for the cfg2-width 250-step streams (kB = 16).
-  static constexpr int kB = 16;
-  __device__ __forceinline__ void twist_chunk(int i0, int cnt) {
-    uint32_t nx[kB + 1], src[kB];
-#pragma unroll
-    for (int u = 0; u <= kB; ++u)
-      if (u <= cnt) nx[u] = k(i0 + u);
-#pragma unroll
-    for (int u = 0; u < kB; ++u)
-      if (u < cnt) {
-        const int i = i0 + u;
-        src[u] = k(i < kN - kM ? i + kM : i + kM - kN);
-      }
-#pragma unroll
-    for (int u = 0; u < kB; ++u)
-      if (u < cnt) {
-        const uint32_t y = (nx[u] & kUpper) | (nx[u + 1] & kLower);
-        k(i0 + u) = src[u] ^ (y >> 1) ^ ((0u - (y & 1u)) & kMatrixA);
-      }
-  }
-
-  __device__ void twist() {
-    for (int i = 0; i < kN - kM; i += kB)          // [0, 227)
-      twist_chunk(i, (kN - kM) - i < kB ? (kN - kM) - i : kB);
-    for (int i = kN - kM; i < kN - 1; i += kB)     // [227, 623)
-      twist_chunk(i, (kN - 1) - i < kB ? (kN - 1) - i : kB);
-    const uint32_t y = (k(kN - 1) & kUpper) | (k(0) & kLower);
-    k(kN - 1) = k(kM - 1) ^ (y >> 1) ^ ((0u - (y & 1u)) & kMatrixA);
-    pos = 0;
-  }
-
-  __device__ __forceinline__ uint32_t next32() {
-    if (pos == kN) twist();
-    uint32_t y = k(pos++);
-    y ^= y >> 11;
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-    y ^= y >> 18;
-    return y;
-  }
-
-  // legacy_double / random_sample
-  __device__ __forceinline__ double next_double() {
-    const int32_t a = (int32_t)(next32() >> 5), b = (int32_t)(next32() >> 6);
-    return (a * 67108864.0 + b) / 9007199254740992.0;
-  }
-  __device__ __forceinline__ void maintain() {}
-};
-
-// The same generator with a DOUBLE-BUFFERED state and a wave-synchronous
-// refill.  A lane consumes block b from buffer `buf`; the other buffer
-// already holds block b + 1, so reaching word 624 only flips `buf` and marks
-// the lane pending (the buffer it left is free).  A pending lane's free
-// buffer is refilled with block b + 2 by an OUT-OF-PLACE twist of its current
-// block -- the sequential twist's result: dst[i] = src[i + 397] (i < 227) or
-// dst[i - 227] (i >= 227) ^ f(src[i], src[i + 1]), dst[623] = dst[396] ^
-// f(src[623], dst[0]) -- and every pending lane of the wave twists together,
-// as soon as any of them is kRefill words into its block.  Lanes drift apart
-// by a few dozen words per block (polar rejections), so a wave twists about
-// once per 624 words instead of once per distinct lane position.  A lane
-// always passes kRefill < 624 before its block ends, so the next block is
-// ready whenever it is needed, whatever the drift.
+// The DOUBLE-BUFFERED state (Mt3's; PBH_LEGACY_K4=0, and the automatic choice
+// once Mt4's state would span 2^32 bytes).  A lane consumes block b from
+// buffer `buf`; the other buffer already holds block b + 1, so reaching word
+// 624 only flips `buf` and marks the lane pending (the buffer it left is
+// free).  A pending lane's free buffer is refilled with block b + 2 by an
+// OUT-OF-PLACE twist of its current block -- the sequential twist's result:
+// dst[i] = src[i + 397] (i < 227) or dst[i - 227] (i >= 227) ^ f(src[i],
+// src[i + 1]), dst[623] = dst[396] ^ f(src[623], dst[0]) -- and every pending
+// lane of the wave twists together, as soon as any of them is 312 words
+// (Mt3::kRefill) into its block.  Lanes drift apart by a few dozen words per
+// block (polar rejections), so a wave twists about once per 624 words instead
+// of once per distinct lane position.  A lane always passes word 312 before
+// its block ends, so the next block is ready whenever it is needed, whatever
+// the drift.
 //
 // Layout [2][156][N] of uint4: a lane's words 4q .. 4q + 3 are one 16-byte
-// quad, so the drifting lanes read their words 16 bytes at a time (a
-// register quad, reloaded every fourth word) and the twist moves whole
-// quads: each quad of dst needs the quad q of src and the first word of quad
-// q + 1, words 4q + 397 .. + 400 (quads q + 99, q + 100, at offset 1) or
-// dst words 4q - 227 .. - 224 (quads q - 57, q - 56, at offset 1).
+// quad, and the twist moves whole quads: each quad of dst needs the quad q of
+// src and the first word of quad q + 1, words 4q + 397 .. + 400 (quads
+// q + 99, q + 100, at offset 1) or dst words 4q - 227 .. - 224 (quads q - 57,
+// q - 56, at offset 1).
 // Per-lane state word: pos | buf << 16 | pending << 17.
 
-
-struct Mt2 {
-  static constexpr bool kLockstep = true;
-  static constexpr bool kPeek = false;
-  static constexpr bool kPeek4 = false;
-  static constexpr bool kLogTab = false;
-  static constexpr int kRefill = 312;
+// The seeding kernel's first twist of chain c, a quad at a time.
+struct SeedTwist {
   uint4 *key;
   int64_t n, c;
-  int pos, buf, pend;
-  uint4 cur;   // the quad holding word pos (valid when pos % 4 != 0)
 
   __device__ __forceinline__ uint4 &q(int b, int i) {
     return key[((int64_t)b * kQ + i) * n + c];
@@ -204,50 +114,13 @@ struct Mt2 {
       q(d, kQ - 1) = o;
     }
   }
-
-  __device__ __forceinline__ void load_cur() {
-    if (pos & 3) cur = q(buf, pos >> 2);
-  }
-
-  __device__ __forceinline__ uint32_t next32() {
-    if (__builtin_amdgcn_ballot_w64(pend && pos >= kRefill)) {   // wave-uniform
-      if (pend) {
-        twist_from(buf);
-        pend = 0;
-      }
-    }
-    if (pos == kN) {
-      buf ^= 1;
-      pos = 0;
-      pend = 1;
-    }
-    const int u = pos & 3;
-    if (u == 0) cur = q(buf, pos >> 2);
-    ++pos;
-    uint32_t y = u == 0 ? cur.x : (u == 1 ? cur.y : (u == 2 ? cur.z : cur.w));
-    y ^= y >> 11;
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-    y ^= y >> 18;
-    return y;
-  }
-
-  __device__ __forceinline__ double next_double() {
-    const int32_t a = (int32_t)(next32() >> 5), b = (int32_t)(next32() >> 6);
-    return (a * 67108864.0 + b) / 9007199254740992.0;
-  }
-
-  __device__ __forceinline__ int packed() const {
-    return pos | (buf << 16) | (pend << 17);
-  }
-  __device__ __forceinline__ void maintain() {}
 };
 
-// The double-buffered state consumed through an LDS WINDOW (the default).
-// Mt2's lanes read their next quad from HBM when they reach it: in the
-// polar-method loop that is one dependent global load per attempt, and at one
-// wavefront per SIMD nothing hides it.  Here each lane's upcoming words are
-// staged in LDS ahead of use: a ring of 2H quads per lane ([slot][256
+// The double-buffered state consumed through an LDS WINDOW (Mt3).  A lane
+// that reads its next quad from HBM when it reaches it makes one dependent
+// global load per attempt of the polar-method loop, and at one wavefront per
+// SIMD nothing hides it.  Here each lane's upcoming words are staged in LDS
+// ahead of use: a ring of 2H quads per lane ([slot][256
 // threads] of uint4, conflict-free whatever the lanes' positions), refilled H
 // quads at a time (H loads in flight) at the top of a step whenever a lane
 // has H or fewer quads left -- the ballot makes the refills wave-wide.  The
@@ -256,7 +129,7 @@ struct Mt2 {
 // block must be twisted before the head enters it (forced here if the step-top
 // trigger at word 312 has not yet run).  A twist overwrites only the block
 // BEFORE the consumption position's, whose words are consumed, so the state
-// in HBM (pos, buf, pend: Mt2's packed word) stays valid when a launch ends
+// in HBM (pos, buf, pend: the packed word above) stays valid when a launch ends
 // with words still in the window.
 //
 // The twist itself runs in batches of 14 quads: part 1 (dst quads 0 .. 55)
@@ -1037,12 +910,9 @@ __global__ __launch_bounds__(256) void mt_seed_db_kernel(uint32_t *key, int32_t 
     }
     qk[(int64_t)i * n + c] = make_uint4(w[0], w[1], w[2], w[3]);
   }
-  Mt2 m{qk, n, c, 0, 0, 0, make_uint4(0u, 0u, 0u, 0u)};
+  SeedTwist m{qk, n, c};
   m.twist_from(0);
-  m.buf = 1;
-  m.pos = 0;
-  m.pend = 1;
-  pos[c] = m.packed();
+  pos[c] = 0 | (1 << 16) | (1 << 17);   // pos 0, buf 1, pending
   gauss[c] = 0.0;
   has_gauss[c] = 0;
 }
@@ -1264,29 +1134,6 @@ __device__ __forceinline__ void legacy_gen_body(const LegacyArgs &a, int64_t c, 
   }
   a.gauss[c] = gauss;
   a.has_gauss[c] = has;
-}
-
-__global__ __launch_bounds__(256) void legacy_gen_kernel(LegacyArgs a) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= a.n) return;
-  Mt m{a.key, a.n, c, a.pos[c]};
-  legacy_gen_body(a, c, m);
-  a.pos[c] = m.pos;
-}
-
-// Lanes past the last chain leave at once; the refill ballot counts the
-// active lanes only.
-__global__ __launch_bounds__(256) void legacy_gen_db_kernel(LegacyArgs a) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= a.n) return;
-  const int st = a.pos[c];
-  Mt2 m{reinterpret_cast<uint4 *>(a.key), a.n, c, st & 0xFFFF, (st >> 16) & 1,
-        (st >> 17) & 1, make_uint4(0u, 0u, 0u, 0u)};
-  m.load_cur();
-  // accepted polar pairs of one step, [pair][thread] (bank-conflict free)
-  __shared__ double2 s_stage[(PBH_MAX_DIM + 1) / 2 * 256];
-  legacy_gen_body(a, c, m, s_stage);
-  a.pos[c] = m.packed();
 }
 
 // The windowed generator (Mt3): dynamic LDS = the lanes' rings (2H quads
@@ -1520,60 +1367,6 @@ struct LegacyDraws {
   }
 };
 
-// ---------------------------------------------------------------------------
-// Timing-only probe (PBH_LEGACY_FAKE=1; wrong streams, never a result): the
-// fused kernel with the Mt4 generator replaced by a counter hash of the same
-// interface -- no state in HBM, no twist, no window -- so that its time is
-// what the polar method, the REPLAY step and the trace cost without MT19937.
-// ---------------------------------------------------------------------------
-struct FakeM {
-  static constexpr bool kLockstep = true, kPeek = true, kPeek4 = true, kLogTab = true;
-  uint32_t ctr, key;
-  __device__ __forceinline__ static uint32_t mix(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-  }
-  __device__ __forceinline__ double dbl(uint32_t i) const {
-    const uint32_t a = mix(i ^ key), b = mix(i + 0x9E3779B9u * key);
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
-  }
-  __device__ __forceinline__ void maintain() {}
-  __device__ __forceinline__ double next_double() { return dbl(ctr++); }
-  __device__ __forceinline__ void attempts4(double (&x1)[4], double (&x2)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      x1[i] = 2.0 * dbl(ctr + 2 * i) - 1.0;
-      x2[i] = 2.0 * dbl(ctr + 2 * i + 1) - 1.0;
-    }
-  }
-  __device__ __forceinline__ void advance(int nw) { ctr += (uint32_t)nw / 2; }
-};
-
-template <int D, bool NORMAL, int TGT, int PROP>
-__global__ __launch_bounds__(kBlockLegacy) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void legacy_mh_fake_kernel(LegacyArgs la, KArgs a) {
-  extern __shared__ w4 s_lw[];
-  __shared__ double s_lg[kLegLogDoubles];
-  for (int i = threadIdx.x; i < kLegLogDoubles; i += kBlockLegacy) s_lg[i] = la.lgtab[i];
-  __syncthreads();
-  const int64_t c = (int64_t)blockIdx.x * kBlockLegacy + threadIdx.x;
-  if (c >= la.n) return;
-  FakeM m{(uint32_t)la.step0 * 64u, (uint32_t)c * 0x85ebca6bu + 1u};
-  LegacyDraws<FakeM, NORMAL> src{m, reinterpret_cast<double2 *>(s_lw), s_lg,
-                                 la.gauss[c], la.has_gauss[c], la.thr, la.n};
-  mh_body<D, PBH_RNG_REPLAY, TGT, PROP>(a, src, nullptr, false);
-  la.gauss[c] = src.gauss;
-  la.has_gauss[c] = src.has;
-}
-
-bool legacy_fake_on() {
-  static const bool on = [] {
-    const char *p = std::getenv("PBH_LEGACY_FAKE");
-    return p && p[0] == '1';
-  }();
-  return on;
-}
-
 template <int D, int H, bool NORMAL, int TGT, int PROP>
 __global__ __launch_bounds__(kBlockLegacy) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void legacy_mh_kernel(LegacyArgs la, KArgs a) {
@@ -1620,16 +1413,6 @@ hipError_t launch_legacy_mh_t(const LegacyArgs &la, const KArgs &a, hipStream_t 
 template <int D>
 hipError_t launch_legacy_mh_d(const LegacyArgs &la, const KArgs &a, hipStream_t s) {
   constexpr int H = D <= 12 ? 16 : 8;   // the window while the stage leaves room
-  if constexpr (D == 10) {
-    if (legacy_fake_on() && la.normal && a.target == PBH_TARGET_DIAG_GAUSS &&
-        a.prop == PBH_PROP_GAUSS) {   // timing-only probe (see FakeM)
-      constexpr size_t lds = (size_t)((D + 1) / 2) * kBlockLegacy * sizeof(uint4);
-      const dim3 grid((unsigned)((la.n + kBlockLegacy - 1) / kBlockLegacy)), block(kBlockLegacy);
-      hipLaunchKernelGGL((legacy_mh_fake_kernel<D, true, PBH_TARGET_DIAG_GAUSS, PBH_PROP_GAUSS>),
-                         grid, block, lds, s, la, a);
-      return hipGetLastError();
-    }
-  }
   if (la.normal) {
     if (a.target == PBH_TARGET_DIAG_GAUSS && a.prop == PBH_PROP_GAUSS)   // cfg2's form
       return launch_legacy_mh_t<D, H, true, PBH_TARGET_DIAG_GAUSS, PBH_PROP_GAUSS>(la, a, s);
@@ -1736,16 +1519,13 @@ hipError_t launch_legacy_ahead(uint32_t *key, int32_t *pos, int64_t n, int32_t w
 
 hipError_t launch_legacy_seed(uint32_t *key, int32_t *pos, double *gauss,
                               int32_t *has_gauss, const uint32_t *seeds,
-                              int64_t n, int32_t db, hipStream_t s) {
+                              int64_t n, bool k4, hipStream_t s) {
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (db == 2)
+  if (k4)
     hipLaunchKernelGGL(mt_seed_k4_kernel, grid, block, 0, s, key, pos, gauss,
                        has_gauss, seeds, n);
-  else if (db)
-    hipLaunchKernelGGL(mt_seed_db_kernel, grid, block, 0, s, key, pos, gauss,
-                       has_gauss, seeds, n);
   else
-    hipLaunchKernelGGL(mt_seed_kernel, grid, block, 0, s, key, pos, gauss,
+    hipLaunchKernelGGL(mt_seed_db_kernel, grid, block, 0, s, key, pos, gauss,
                        has_gauss, seeds, n);
   return hipGetLastError();
 }
@@ -1755,7 +1535,7 @@ hipError_t launch_legacy_wp(const LegacyArgs &a, hipStream_t s);
 
 hipError_t launch_legacy_draws(const LegacyArgs &a, int32_t kind, double param,
                                hipStream_t s) {
-  if (a.db != 2) return hipErrorNotSupported;   // the Mt4 state
+  if (!a.k4) return hipErrorNotSupported;   // the Mt4 state
   constexpr int H = 16;
   const size_t lds = (size_t)(2 * H) * kBlockLegacy * sizeof(uint4);
   hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&legacy_draws_kernel<H>),
@@ -1768,22 +1548,12 @@ hipError_t launch_legacy_draws(const LegacyArgs &a, int32_t kind, double param,
 
 hipError_t launch_legacy_gen(const LegacyArgs &a, hipStream_t s) {
   // the word-parallel generator: Mt4's state, MH streams of doubles
-  if (a.db == 2 && a.wp && !a.gibbs && !a.vardelta) return launch_legacy_wp(a, s);
-  if (a.db == 2) {   // Mt4: four chunked blocks through the window
-    if (!a.normal || a.d <= 12) return launch_k4<16>(a, s);
-    return launch_k4<8>(a, s);
-  }
-  if (a.db && a.win) {
-    // 2H = 32 quads (128 words) per lane while the stage leaves room
-    if (!a.normal || a.d <= 12) return launch_win<16>(a, s);
-    return launch_win<8>(a, s);
-  }
-  const dim3 grid((unsigned)((a.n + 255) / 256)), block(256);
-  if (a.db)
-    hipLaunchKernelGGL(legacy_gen_db_kernel, grid, block, 0, s, a);
-  else
-    hipLaunchKernelGGL(legacy_gen_kernel, grid, block, 0, s, a);
-  return hipGetLastError();
+  if (a.k4 && a.wp && !a.gibbs && !a.vardelta) return launch_legacy_wp(a, s);
+  // 2H = 32 quads (128 words) per lane while the stage leaves room
+  const bool wide = !a.normal || a.d <= 12;
+  if (a.k4)   // Mt4: chunked blocks through the window
+    return wide ? launch_k4<16>(a, s) : launch_k4<8>(a, s);
+  return wide ? launch_win<16>(a, s) : launch_win<8>(a, s);   // Mt3
 }
 
 // The fused REPLAY kernel for the forms it covers (see legacy_mh_kernel):
@@ -1797,7 +1567,7 @@ bool legacy_mh_dim(int d) {
 }
 
 hipError_t launch_legacy_mh(const LegacyArgs &la, const KArgs &a, hipStream_t s, bool check) {
-  if (la.db != 2 || la.gibbs || la.vardelta || la.d != a.d || !legacy_mh_dim(la.d) ||
+  if (!la.k4 || la.gibbs || la.vardelta || la.d != a.d || !legacy_mh_dim(la.d) ||
       !(la.normal ? a.prop == PBH_PROP_GAUSS
                   : (a.prop == PBH_PROP_UNIFORM || a.prop == PBH_PROP_SPHERE)))
     return hipErrorNotSupported;

@@ -477,7 +477,7 @@ class Engine:
     mt = ck.get('mt')
     if mt is not None:
       # the C side copies words x N, N, N, N values from these arrays: a
-      # checkpoint of the other legacy layout (PBH_LEGACY_DB) or of another
+      # checkpoint of the other legacy layout (PBH_LEGACY_K4) or of another
       # chain count would be read past its end
       words = _c.c_int64()
       _lib.call('pbh_legacy_state_words', self._h, _c.byref(words))
@@ -485,8 +485,8 @@ class Engine:
               'gauss': (self.n,)}
       layouts = {640: 'Mt4, its current chunked block (the default since round 6)',
                  2560: 'Mt4, four chunked blocks (rounds 4-5)',
-                 1248: 'double-buffered window (PBH_LEGACY_K4=0, round 3)',
-                 624: 'in-place state (PBH_LEGACY_DB=0, round 1)'}
+                 1248: 'double-buffered window (PBH_LEGACY_K4=0, and the automatic '
+                       'choice from 104 858 chains)'}
       for k, shape in want.items():
         got = np.shape(mt[k])
         if got != shape:
@@ -497,6 +497,9 @@ class Engine:
                     'environment'.format(
                         layouts.get(got[0], '{}-word'.format(got[0])),
                         layouts.get(words.value, '{}-word'.format(words.value))))
+            if got[0] == 624:
+              hint = ('; the checkpoint holds the round-1 in-place layout, which '
+                      'is gone: no engine restores it')
           raise ValueError('checkpoint legacy state {} has shape {}, this engine '
                            'needs {} (legacy layout words per chain: {}){}'.format(
                                k, got, shape, words.value, hint))

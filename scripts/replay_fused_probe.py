@@ -42,6 +42,6 @@ for form in forms:
   eng.sync()
   el = time.perf_counter() - t0
   eng.close()
-  print(json.dumps({'form': form, 'pair': os.environ.get('PBH_LEGACY_PAIR', '1'), 'n': n, 'steps': steps, 'spl': spl,
+  print(json.dumps({'form': form, 'n': n, 'steps': steps, 'spl': spl,
                     'ms_per_launch': el * 1e3 / (steps / spl),
                     'chain_steps_per_s': n * steps / el}), flush=True)

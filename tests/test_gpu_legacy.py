@@ -93,6 +93,48 @@ def test_device_streams_equal_numpy_randomstate(name):
   np.testing.assert_array_equal(thr, dev[:, -1, :])
 
 
+@pytest.mark.parametrize('name', ['diag10', 'gauss5_permuted', 'gibbs8', 'randint_wide'])
+def test_double_buffered_fallback_streams_equal_numpy_randomstate(monkeypatch, name):
+  """The double-buffered state through the LDS window (PBH_LEGACY_K4=0), which
+  an engine takes by itself from 104 858 chains on (the four-block state would
+  span 2^32 bytes), at a small chain count: a full 256-lane workgroup and a
+  ragged one, normal draws with an even and an odd d, Gibbs rows, randint's
+  single words; 80 steps of diag10 are ~2 200 words per chain, so the streams
+  cross three block refills and use both buffers.  A checkpoint restored in a
+  second such engine continues the uninterrupted streams."""
+  monkeypatch.setenv('PBH_LEGACY_K4', '0')
+  spec = _specs()[name]
+  n, t, more = 261, 80, 20
+  seeds = np.concatenate([[0, 1, 2 ** 32 - 1, 123456789],
+                          np.arange(1000, 1000 + n - 4)])
+  ref = oracle.legacy_streams(spec, seeds, t + more)
+  d = int(spec['dim'])
+  normal = set(range(d)) if spec['proposal']['kind'] == 'gauss' else set()
+  eng = _engine(spec, n, seeds)
+  eng.legacy_replay(t)
+  dev = eng.get_replay(0, t)
+  thr = eng.get_replay(0, t, eng.stream_width() - 1)
+  ck = eng.checkpoint()
+  if name == 'diag10':   # two 624-word blocks per chain
+    import ctypes
+    from probayes_amd import _lib
+    words = ctypes.c_int64()
+    _lib.call('pbh_legacy_state_words', eng._h, ctypes.byref(words))
+    assert words.value == 1248
+    assert ck['mt']['key'].shape == (1248, n)
+  eng.close()
+  _check(dev, ref[:t], normal)
+  np.testing.assert_array_equal(thr, dev[:, -1, :])
+  # the chains were not run: the checkpoint's step is set to the streams'
+  # (the Gibbs cycle phase of the next row)
+  eng = _engine(spec, n, seeds[::-1])   # other streams until the restore
+  eng.restore(dict(ck, step=t))
+  eng.legacy_replay(more)
+  rest = eng.get_replay(0, more)
+  eng.close()
+  _check(rest, ref[t:], normal)
+
+
 def test_device_streams_continue_across_calls():
   spec = _specs()['gauss5_permuted']
   n = 64

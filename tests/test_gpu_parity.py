@@ -534,25 +534,20 @@ def test_gmm_quad_full_size_cfg5_is_the_general_form(monkeypatch):
   assert ta['n_acc'].min() > 0   # every chain moved
 
 
-@pytest.mark.parametrize('pair', ['1', '0'])
 @pytest.mark.parametrize('n', [4096 + 5, 37])
-def test_iid_steady_state_form_is_the_general_form(monkeypatch, pair, n):
+def test_iid_steady_state_form_is_the_general_form(monkeypatch, n):
   """cfg1's steady-state launch (iid-Normal target, spherical delta, ufun on
-  sigma, uniform prior, e-tempered ratio form) -- on one lane per chain
-  (mh_iid_full_kernel, the default, PBH_IID_PAIR=0) or on lane pairs
-  (mh_iid_pair_kernel, opt-in PBH_IID_PAIR=1, measured slower) -- is
-  bit-for-bit mh_kernel's general form
-  (PBH_IID_FULL=0): ragged chain counts (padding lanes write nothing; an odd
-  number of 32-chain wavefronts leaves the last accept word half-owned),
-  launches of 1 and 13 steps starting on either step of a pair, chains
-  started outside the prior box (density -inf until they enter it)."""
+  sigma, uniform prior, e-tempered ratio form) on one lane per chain
+  (mh_iid_full_kernel) is bit-for-bit mh_kernel's general form
+  (PBH_IID_FULL=0): ragged chain counts (padding lanes write nothing),
+  launches of 1 and 13 steps, chains started outside the prior box (density
+  -inf until they enter it)."""
   from probayes_amd import Engine
   spec = oracle.golden_spec('metrohast_norm1d')
   t = 61
   init = golden_init('metrohast_norm1d', n)
   init[::89, 1] = 30.   # sigma outside (5, 20)
   outs = {}
-  monkeypatch.setenv('PBH_IID_PAIR', pair)
   for full in ('1', '0'):
     monkeypatch.setenv('PBH_IID_FULL', full)
     eng = Engine(spec)
