@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pbh_philox.h"   // u32x4, PhiloxKeys, the factored first rounds
+
 namespace pbh {
 
 // constants.py:9-35 (64-bit precision)
@@ -24,8 +26,6 @@ constexpr double kNearlyNegInf = -1.7976931348623158e+308;
 // the stream of chain c at step g is a pure function of (seed, c, g), so
 // traces are identical for any sharding of chains over GPUs.
 // ---------------------------------------------------------------------------
-struct u32x4 { uint32_t x, y, z, w; };
-
 __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0,
                                                 uint32_t k1) {
   constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
@@ -49,7 +49,6 @@ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0,
 // the steady-state loops run short of SGPRs, and a uniform value the
 // compiler demotes on its own costs a readfirstlane loop per buffer store).
 // The v_mov is an asm so that the result counts as divergent.
-struct PhiloxKeys { uint32_t k0[10], k1[10]; };
 __device__ __forceinline__ uint32_t in_vgpr(uint32_t v) {
   uint32_t r;
   asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(v));

@@ -1641,7 +1641,8 @@ int pbh_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
   if (e->srv_active && (steps_per_launch <= 0 || steps_per_launch >= n_steps) &&
       n_steps <= (1 << 30) && e->g + n_steps < (int64_t(1) << 47) &&
       !(e->collect & PBH_COLLECT_MOMENTS) && e->has_pred && e->cap > 0 && e->thin == 1 &&
-      e->g - e->rec_base >= 0 && e->g + n_steps - e->rec_base <= e->cap) {
+      e->g - e->rec_base >= 0 && e->g + n_steps - e->rec_base <= e->cap &&
+      pbh::pair_index_hi_const(e->g, n_steps)) {
     if (e->srv_pending) {
       const int rc = srv_wait(e, e->srv_pending, false);
       e->srv_pending = 0;
@@ -1684,7 +1685,8 @@ int pbh_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
     const bool form = e->g + n_steps < (int64_t(1) << 47) &&   // srv_arg's 48-bit step
         (e->srv_active
              ? (!k.moments && e->has_pred && e->cap > 0 && e->thin == 1 &&
-                e->g - e->rec_base >= 0 && e->g + n_steps - e->rec_base <= e->cap)
+                e->g - e->rec_base >= 0 && e->g + n_steps - e->rec_base <= e->cap &&
+                pbh::pair_index_hi_const(e->g, n_steps))
              : pbh::launch_mh_server(kc, e->stream, &wgs, true) == hipSuccess);
     if (form) {
       if (e->srv_active) {

@@ -202,6 +202,13 @@ inline bool gibbs_fast_form(const KArgs &a) {
   return a.gibbs_fast && a.rng == 1 /* PBH_RNG_PHILOX */ && !a.debug && a.d <= 16;
 }
 
+// Steps [g0, g0 + n) lie in step pairs (step / 2) whose index has one high
+// word: the FULL lane-pair kernel's factored Philox rounds (PhiloxPrefix) are
+// built for it.  A run that crosses 2^32 pairs takes the general form.
+inline bool pair_index_hi_const(int64_t g0, int64_t n) {
+  return n < 1 || (g0 >> 33) == ((g0 + n - 1) >> 33);
+}
+
 // Host launchers (pbh_kernels.hip).
 hipError_t launch_mh(const KArgs &a, hipStream_t s, size_t lds_bytes);
 hipError_t launch_gibbs(const KArgs &a, hipStream_t s);

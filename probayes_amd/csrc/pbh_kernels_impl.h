@@ -108,9 +108,7 @@ __device__ __forceinline__ void xo_store(const KArgs &a, int h, int64_t c,
 }
 
 __device__ __forceinline__ u32x4 ctr(uint32_t j, int64_t g, int64_t chain) {
-  return u32x4{j, (uint32_t)g, (uint32_t)chain,
-               (uint32_t)((uint64_t)chain >> 32) ^
-                   ((uint32_t)((uint64_t)g >> 32) << 16)};
+  return philox_ctr(j, g, chain);
 }
 
 // Production Gaussian draws of one chain-step (mh_kernel and the GMM
@@ -1465,29 +1463,21 @@ void mh_pair_kernel(KArgs a) {
         const uint32_t aoff = lane == 32 ? (uint32_t)((c >> 5) * 4) : kNoStore;
         const uint32_t abytes = (uint32_t)(a.W * 8);
         int64_t rec = g0v + s - a.rec_base;   // thin 1: record = step
+        // Philox: round keys 3..9 in VGPRs; rounds 1-3 of a pair's NB blocks
+        // come factored (pbh_philox.h) from per-lane words that hold for one
+        // value of the pair index's high word -- a launch or command never
+        // crosses one (pair_full_form), so they are built here and, SRV, again
+        // at the entry of a command whose high word differs
         const PhiloxKeys rk = philox_keys_v(a.seed_lo, a.seed_hi);
+        uint32_t pre_hi = (uint32_t)((uint64_t)g0v >> 33);
+        PhiloxPrefix<NB> pre =
+            philox_prefix<NB>(16u * (uint32_t)h, chain, pre_hi, a.seed_lo, a.seed_hi);
         // blocks Q0 .. NB-1 of pair P (the words before block Q0 unused)
         auto philox_from = [&](int64_t P, uint32_t (&w)[4 * NB], auto Q0) {
-#pragma unroll
-          for (int q = 0; q < 4 * decltype(Q0)::value; ++q) w[q] = 0u;
-#pragma unroll
-          for (int q = decltype(Q0)::value; q < NB; ++q) {
-            const u32x4 b = philox4x32_10_rk(ctr(q + 16 * h, P, chain), rk);
-            w[4 * q] = b.x;
-            w[4 * q + 1] = b.y;
-            w[4 * q + 2] = b.z;
-            w[4 * q + 3] = b.w;
-          }
+          philox_prefix_blocks<NB, decltype(Q0)::value>((uint32_t)P, pre, rk, w);
         };
         auto philox = [&](int64_t P, uint32_t (&w)[4 * NB]) {
-#pragma unroll
-          for (int q = 0; q < NB; ++q) {
-            const u32x4 b = philox4x32_10_rk(ctr(q + 16 * h, P, chain), rk);
-            w[4 * q] = b.x;
-            w[4 * q + 1] = b.y;
-            w[4 * q + 2] = b.z;
-            w[4 * q + 3] = b.w;
-          }
+          philox_prefix_blocks<NB>((uint32_t)P, pre, rk, w);
         };
         // Box-Muller pairs q0 <= q < q1 of a pair's words into the two steps'
         // normals (PairDraw's layout)
@@ -1696,6 +1686,10 @@ void mh_pair_kernel(KArgs a) {
             // barrier: every wave has read it by then)
             s = 0;
             rec = g0v - a.rec_base;
+            if ((uint32_t)((uint64_t)g0v >> 33) != pre_hi) {   // wave-uniform
+              pre_hi = (uint32_t)((uint64_t)g0v >> 33);
+              pre = philox_prefix<NB>(16u * (uint32_t)h, chain, pre_hi, a.seed_lo, a.seed_hi);
+            }
             run_block();
             __builtin_amdgcn_s_waitcnt(0);   // this wave's stores have left
             __syncthreads();
@@ -3224,7 +3218,8 @@ inline bool pair_full_form(const KArgs &a) {
   return a.pair_full && a.rng == PBH_RNG_PHILOX && a.has_pred && a.thin == 1 &&
          a.pscale != PBH_PSCALE_LIN && a.tx != nullptr && a.n % 32 == 0 &&
          a.n * 8 <= (int64_t)kNoStore &&   // masked stores: kNoStore out of range
-         a.g0 - a.rec_base >= 0 && a.g0 + a.n_steps - a.rec_base <= a.rec_cap;
+         a.g0 - a.rec_base >= 0 && a.g0 + a.n_steps - a.rec_base <= a.rec_cap &&
+         pair_index_hi_const(a.g0, a.n_steps);
 }
 
 // cfg1's steady-state form applies (see mh_iid_full_kernel): production
