@@ -30,8 +30,9 @@ extern "C" {
 #define PBH_ABI_VERSION 7
 /* Additions that leave every version-7 call and struct prefix as it was bump
  * the revision: 1 = pbh_model.expr_data / expr_n_obs / expr_n_cols (a caller
- * passes the whole struct, zero-initialised), pbh_eval_expr_data.            */
-#define PBH_ABI_REVISION 1
+ * passes the whole struct, zero-initialised), pbh_eval_expr_data;
+ * 2 = pbh_trace_quantile.                                                   */
+#define PBH_ABI_REVISION 2
 #define PBH_MAX_DIM 32
 
 #define PBH_OK 0
@@ -453,6 +454,28 @@ int pbh_trace_stats(pbh_engine *eng, int64_t first, int64_t count, double *sum,
  * order.  out [d][N] on the host.                                           */
 int pbh_trace_expectation(pbh_engine *eng, int64_t first, int64_t count,
                           double exponent, double *out);
+/* summary.sorted(key).quantile(q)[key] over trace records [first, first +
+ * count) on the device (pd.py:408-493), for every chain and every key: each
+ * dim k is sorted by itself (after sorted(key) only the sort key is
+ * monotonic; the reference gives {size} for the others), ascending, ties by
+ * record index, NaN last; out[j][k][c] is PD.quantile(q[j]) of chain c's
+ * summary sorted by dim k, for key k.  weighted = 1: the weights are the
+ * recorded v.prob rescaled to linear (as pbh_trace_expectation); weighted =
+ * 0: unit weights, the plain empirical quantile -- PD(vals, prob = ones,
+ * pscale = 'lin') on the host, which it equals bit for bit (with weights,
+ * to the device's exp).  The arithmetic is the reference's: cumprob =
+ * cumsum(p) / max(tiny, sum p), idx = max(0, #{cumprob <= q} - 1), the last
+ * record's value at idx = count - 1, else np.interp between the records idx
+ * and idx + 1 when |p1 - p0| < min(q, 1 - q), else their p-weighted mean.
+ * 1 <= count <= PBH_QUANTILE_MAX_RECORDS (a series is sorted in LDS), 1 <=
+ * nq <= PBH_QUANTILE_MAX_Q, every q[j] in [0, 1]; out [nq][d][N] on the
+ * host.  Changes nothing in the engine: not the moments (unlike
+ * pbh_trace_stats), the ESS, the trace, the chains or the generators.       */
+#define PBH_QUANTILE_MAX_RECORDS 2048
+#define PBH_QUANTILE_MAX_Q 64
+int pbh_trace_quantile(pbh_engine *eng, int64_t first, int64_t count,
+                       int32_t nq, const double *q, int32_t weighted,
+                       double *out);
 
 /* ---- multi-GPU: one RCCL all-gather over xGMI --------- */
 int pbh_rccl_unique_id(uint8_t id[128]);

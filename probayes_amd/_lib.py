@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PBHIP_LIB', os.path.join(_HERE, 'libpbhip.so'))
 
 ABI_VERSION = 7
-ABI_REVISION = 1   # PBH_ABI_REVISION: additions within version 7
+ABI_REVISION = 2   # PBH_ABI_REVISION: additions within version 7
 DRAWS_GAUSS, DRAWS_LINREG = 0, 1   # enum pbh_draws
 MAX_DIM = 32
 
@@ -153,6 +153,9 @@ SIGNATURES = {
     'pbh_trace_expectation': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_double,
                                              _dp]),
+    'pbh_trace_quantile': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.c_int64, ctypes.c_int32, _dp,
+                                          ctypes.c_int32, _dp]),
     'pbh_trace_ess': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
                                      ctypes.c_int64, _dp]),
     'pbh_rccl_allreduce_max': (ctypes.c_int, [ctypes.c_void_p, _dp]),

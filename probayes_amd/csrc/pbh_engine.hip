@@ -2350,6 +2350,48 @@ int pbh_trace_expectation(pbh_engine *e, int64_t first, int64_t count,
   return PBH_OK;
 }
 
+int pbh_trace_quantile(pbh_engine *e, int64_t first, int64_t count, int32_t nq,
+                       const double *q, int32_t weighted, double *out) {
+  if (check_ptr(e, "engine") || check_ptr(q, "q") || check_ptr(out, "out"))
+    return PBH_ERR_ARG;
+  SRV_STOP(e);
+  if (e->cap <= 0 || !e->tx || !e->tlp)
+    return fail(PBH_ERR_ARG, "no trace allocated (pbh_alloc_trace first)");
+  if (nq < 1 || nq > PBH_QUANTILE_MAX_Q)
+    return fail(PBH_ERR_ARG, "nq = %d outside 1..%d", (int)nq, PBH_QUANTILE_MAX_Q);
+  for (int32_t j = 0; j < nq; ++j)
+    if (!(q[j] >= 0. && q[j] <= 1.))
+      return fail(PBH_ERR_ARG, "q[%d] = %g is not a quantile in [0, 1]", (int)j, q[j]);
+  if (count < 1) return fail(PBH_ERR_ARG, "count = %lld: at least 1 record", (long long)count);
+  if (count > PBH_QUANTILE_MAX_RECORDS)
+    return fail(PBH_ERR_ARG, "count = %lld above the %d records a series is sorted at",
+                (long long)count, PBH_QUANTILE_MAX_RECORDS);
+  int64_t rec = 0;
+  pbh_trace_len(e, &rec);
+  if (first < 0 || first > rec || count > rec - first)
+    return fail(PBH_ERR_ARG, "trace range [%lld, %lld) outside [0, %lld)",
+                (long long)first, (long long)(first + count), (long long)rec);
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t res = (size_t)nq * e->d * e->n;
+  double *dbuf = nullptr;   // q [nq], then the result [nq][d][n]
+  HIP_TRY(hipMalloc(&dbuf, (PBH_QUANTILE_MAX_Q + res) * sizeof(double)));
+  hipError_t err = hipMemcpyAsync(dbuf, q, nq * sizeof(double), hipMemcpyHostToDevice,
+                                  e->stream);
+  if (err == hipSuccess)
+    err = pbh::launch_trace_quantile(e->tx, e->tlp, e->n, e->d, first, (int32_t)count, nq,
+                                     dbuf, weighted ? 1 : 0,
+                                     e->k.pscale == PBH_PSCALE_LIN ? 1 : 0, e->k.log_npi,
+                                     dbuf + PBH_QUANTILE_MAX_Q, e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess)
+    err = hipMemcpy(out, dbuf + PBH_QUANTILE_MAX_Q, res * sizeof(double),
+                    hipMemcpyDeviceToHost);
+  (void)hipFree(dbuf);
+  if (err != hipSuccess)
+    return fail(PBH_ERR_HIP, "pbh_trace_quantile: %s", hipGetErrorString(err));
+  return PBH_OK;
+}
+
 int pbh_trace_ess(pbh_engine *e, int64_t first, int64_t count, double *ess) {
   if (check_ptr(e, "engine")) return PBH_ERR_ARG;
   SRV_STOP(e);

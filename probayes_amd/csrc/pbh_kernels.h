@@ -237,6 +237,13 @@ hipError_t launch_trace_expectation(const double *tx, const double *tlp,
                                     int64_t n, int32_t d, int64_t first,
                                     int64_t count, double exponent, int32_t lin,
                                     double log_npi, double *out, hipStream_t s);
+// PD.sorted(key).quantile(q)[key] per (chain, dim) of trace records [first,
+// first + count), 1 <= count <= 2 048, 1 <= nq <= 64 (pbh_quantile.hip);
+// q [nq] and out [nq][d][n] on the device
+hipError_t launch_trace_quantile(const double *tx, const double *tlp, int64_t n,
+                                 int32_t d, int64_t first, int32_t count, int32_t nq,
+                                 const double *q, int32_t weighted, int32_t lin,
+                                 double log_npi, double *out, hipStream_t s);
 // fft: 2 = the 2 048-point FFT form for count <= 1 536 records with the
 // 4 096-point form for the pairs it cannot decide (list: (d n + 1) / 2 + 1
 // int32 of device scratch), 1 = the 4 096-point form for count <= 2 048

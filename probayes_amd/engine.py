@@ -633,6 +633,24 @@ class Engine:
               _dp(out))
     return out.T.copy()
 
+  def trace_quantile(self, q, first=0, count=None, weighted=True):
+    """summary.sorted(key).quantile(q)[key] (pd.py:408-493) of trace records
+    [first, first + count) for every chain and every key, computed on the
+    device: [nq, N, d], or [N, d] for a scalar q.  Each dim is sorted by
+    itself.  weighted: the recorded prob rescaled to linear as weights;
+    otherwise unit weights (the empirical quantile).  count is at most 2 048
+    records (PBH_QUANTILE_MAX_RECORDS), nq at most 64."""
+    count = self.trace_len() - first if count is None else count
+    scalar = np.isscalar(q)
+    qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, float)).ravel())
+    out = np.empty((max(qs.size, 1), self.dim, self.n))
+    _lib.call('pbh_trace_quantile', self._h, _c.c_int64(int(first)),
+              _c.c_int64(int(count)), _c.c_int32(qs.size),
+              _dp(qs if qs.size else np.zeros(1)), _c.c_int32(1 if weighted else 0),
+              _dp(out))
+    res = out.transpose(0, 2, 1).copy()
+    return res[0] if scalar else res
+
   def rccl_allreduce_max(self, value):
     v = _c.c_double(float(value))
     _lib.call('pbh_rccl_allreduce_max', self._h, _c.byref(v))

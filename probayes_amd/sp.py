@@ -965,6 +965,8 @@ class Sampler:
     self._prev = None       # the state before the next block, when known on the host
     self._ref = weakref.ref(self)   # the SP registry's key for this sampler
     self._gibbs = None      # _is_gibbs(), fixed once lowered
+    self._eng_blocks = 0    # blocks the engine has run
+    self._trace_block = None   # the block whose records the engine's trace holds
 
   def __repr__(self):
     return '<probayes_amd Sampler {} stop={}>'.format(self.sid, self.stop)
@@ -1086,6 +1088,7 @@ class Sampler:
         eng.set_rng(self.rng, self.seed)
     else:
       self._eng.set_chains(init, np.zeros(self.n), g, False)
+      self._trace_block = None   # (set_chains detaches the trace)
     self._g = g
     self._epoch_first = True
     # the state before the epoch's first step: init, lp 0 (as init_chains /
@@ -1168,6 +1171,9 @@ class Sampler:
     # the next block's predecessor state: this block's last record (read
     # from the host copy _settle makes before that block runs)
     cur = self._cur
+    if self.spec.get('kind') != 'linreg':
+      self._eng_blocks += 1
+      self._trace_block = cur
     self._prev = None if self._is_gibbs() else _LazyPrev(cur)   # (MH: lp = v.prob)
 
   def _compute_engine(self, k, rewind):
@@ -1309,6 +1315,7 @@ class Sampler:
     cur = self._cur
     if cur is None or self._j >= cur.T:
       return   # nothing ahead
+    self._trace_block = None   # the engine's trace is detached or overwritten below
     b, j = self._handed if self._handed is not None else (cur, -1)
     if b is not cur:
       return
@@ -1349,6 +1356,35 @@ class Sampler:
     self._cur, self._j = None, 0
 
   # ---- summaries -------------------------------------------------------------
+  def trace_quantile(self, q, first=0, count=None, weighted=True):
+    """summary.v.sorted(name).quantile(q)[name] for every name and chain,
+    computed by the engine from its device trace (Engine.trace_quantile)
+    without copying the trace to the host: {name: [nq, N]}, or {name: [N]}
+    for a scalar q.  Covers records [first, first + count) of the sampler's
+    first block while the engine still holds it -- for a sampler with stop=T
+    that block is all T steps, and the result is SP(samples).v.sorted(name)
+    .quantile(q)[name] chain by chain.  weighted=False takes unit weights
+    instead of v.prob.  At most 2 048 records."""
+    if not self.batched:
+      raise ValueError('trace_quantile needs a batched sampler (chains=N)')
+    if self.spec is not None and self.spec.get('kind') == 'linreg':
+      raise ValueError('trace_quantile: a linreg sampler keeps no engine trace')
+    if self._eng is None:
+      raise ValueError('trace_quantile: the sampler has no engine (no step has '
+                       'run yet, or it was closed)')
+    blk = self._trace_block
+    if blk is None or self._eng_blocks != 1:
+      raise ValueError('trace_quantile: the engine\'s trace is no longer the '
+                       'first block\'s (another block ran, or the chains were '
+                       'rewound or reset)')
+    first = int(first)
+    count = blk.T - first if count is None else int(count)
+    if first < 0 or count < 1 or first + count > blk.T:
+      raise ValueError('trace_quantile: records [{}, {}) outside the block\'s '
+                       '[0, {})'.format(first, first + count, blk.T))
+    res = self._eng.trace_quantile(q, first, count, weighted)
+    return {k: res[..., i] for i, k in enumerate(self.names)}
+
   @staticmethod
   def _runs(steps):
     """(block, record indices) per run of consecutive steps from one block."""
