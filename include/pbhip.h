@@ -31,7 +31,8 @@ extern "C" {
 /* Additions that leave every version-7 call and struct prefix as it was bump
  * the revision: 1 = pbh_model.expr_data / expr_n_obs / expr_n_cols (a caller
  * passes the whole struct, zero-initialised), pbh_eval_expr_data;
- * 2 = pbh_trace_quantile.                                                   */
+ * 2 = pbh_trace_quantile.  pbh_trace_rhat was added within revision 2
+ * without a bump: a caller finds it by looking the symbol up.               */
 #define PBH_ABI_REVISION 2
 #define PBH_MAX_DIM 32
 
@@ -476,6 +477,36 @@ int pbh_trace_expectation(pbh_engine *eng, int64_t first, int64_t count,
 int pbh_trace_quantile(pbh_engine *eng, int64_t first, int64_t count,
                        int32_t nq, const double *q, int32_t weighted,
                        double *out);
+/* Cross-chain convergence over trace records [first, first + count) on the
+ * device, per dim (added within revision 2: PBH_ABI_REVISION did not change
+ * for it, so a caller that may meet an older revision-2 library finds out by
+ * looking the symbol up).
+ * split_rhat [d]: split-R-hat (Gelman et al., BDA3; Vehtari et al. 2021,
+ * without rank normalisation).  h = count / 2; every chain gives the split
+ * chains [first, first + h) and [first + count - h, first + count) (an odd
+ * count drops the middle record).  Over the 2N split chains with mean m_j and
+ * variance s2_j (ddof 1): W = mean_j s2_j, B/h = var_j m_j (ddof 1), R-hat =
+ * sqrt(((h - 1) / h W + B/h) / W).  Needs count >= 4.
+ * nested_rhat [d]: nested R-hat (Margossian et al. 2024).  Chain c belongs to
+ * superchain c / group; the caller starts a superchain's chains at one point.
+ * With per-chain mean m_c and variance s2_c (ddof 1) over the whole window,
+ * per superchain mu_k = mean_c m_c, B_k = var_c m_c (ddof 1; 0 at group = 1),
+ * W_k = mean_c s2_c: nR-hat = sqrt(1 + var_k mu_k / mean_k (B_k + W_k)), var_k
+ * at ddof 1.  Needs count >= 2, group >= 1, N % group == 0, N / group >= 2;
+ * group is read only when nested_rhat is given.
+ * chain_stats [6][d][N]: mean and variance of the first half, of the second
+ * half and of the whole window, per chain -- all either statistic needs, so
+ * the rows of several ranks concatenated in chain order give the pooled
+ * statistic on the host (probayes_amd/diag.py).  With count < 4 the half
+ * variances are 0/0.
+ * Each of the three may be NULL.  The values are the IEEE results of the
+ * formulas with no special cases: all chains constant and equal give NaN,
+ * constant but different +inf, and a NaN record propagates.  Sums run in a
+ * fixed order: two calls on one trace give the same bits.  Changes nothing in
+ * the engine: not the moments, the ESS, the trace, the chains or the
+ * generators.                                                               */
+int pbh_trace_rhat(pbh_engine *eng, int64_t first, int64_t count, int32_t group,
+                   double *split_rhat, double *nested_rhat, double *chain_stats);
 
 /* ---- multi-GPU: one RCCL all-gather over xGMI --------- */
 int pbh_rccl_unique_id(uint8_t id[128]);

@@ -156,7 +156,11 @@ SIGNATURES = {
     'pbh_trace_quantile': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
                                           ctypes.c_int64, ctypes.c_int32, _dp,
                                           ctypes.c_int32, _dp]),
-    'pbh_trace_ess': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
+    # (added within ABI revision 2: ABI_REVISION did not change for it)
+    'pbh_trace_rhat': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
+                                      ctypes.c_int64, ctypes.c_int32, _dp, _dp,
+                                      _dp]),
+    'pbh_trace_ess':(ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
                                      ctypes.c_int64, _dp]),
     'pbh_rccl_allreduce_max': (ctypes.c_int, [ctypes.c_void_p, _dp]),
     'pbh_rccl_destroy': (ctypes.c_int, [ctypes.c_void_p]),

@@ -90,6 +90,8 @@ struct pbh_engine {
   int64_t ess_list_len = 0;
   double *ess_host = nullptr;    // pinned staging of the ESS copy-out
   int64_t ess_host_len = 0;
+  double *rhat = nullptr;        // pbh_trace_rhat's scratch, kept between calls
+  int64_t rhat_len = 0;
   bool spin_sync = true;     // poll <= 2 ms, then block; PBH_SYNC=block: block
   bool sync_event = false;   // PBH_SYNC=event: poll the last run's end event
   // timing events as marker packets around the launches (default), or
@@ -738,6 +740,7 @@ int pbh_destroy(pbh_engine *e) {
   put(e->msum); put(e->msq); put(e->nacc);
   put(e->gather_send); put(e->gather_recv); put(e->scalar);
   put(e->bm64); put(e->ess); put(e->lgtab); dfree(e->ess_list); put(e->ess_tot);
+  put(e->rhat);
   if (e->ess_host) (void)hipHostFree(e->ess_host);
   if (e->srv_cmd) (void)hipHostFree(e->srv_cmd);
   if (e->srv_done) (void)hipHostFree(e->srv_done);
@@ -2389,6 +2392,63 @@ int pbh_trace_quantile(pbh_engine *e, int64_t first, int64_t count, int32_t nq,
   (void)hipFree(dbuf);
   if (err != hipSuccess)
     return fail(PBH_ERR_HIP, "pbh_trace_quantile: %s", hipGetErrorString(err));
+  return PBH_OK;
+}
+
+int pbh_trace_rhat(pbh_engine *e, int64_t first, int64_t count, int32_t group,
+                   double *split_rhat, double *nested_rhat, double *chain_stats) {
+  if (check_ptr(e, "engine")) return PBH_ERR_ARG;
+  SRV_STOP(e);
+  if (e->cap <= 0 || !e->tx)
+    return fail(PBH_ERR_ARG, "no trace allocated (pbh_alloc_trace first)");
+  int64_t rec = 0;
+  pbh_trace_len(e, &rec);
+  if (first < 0 || first > rec || count < 0 || count > rec - first)
+    return fail(PBH_ERR_ARG, "trace range [%lld, %lld) outside [0, %lld)",
+                (long long)first, (long long)(first + count), (long long)rec);
+  if (count < 2)
+    return fail(PBH_ERR_ARG, "count = %lld: a variance needs at least 2 records",
+                (long long)count);
+  if (split_rhat && count < 4)
+    return fail(PBH_ERR_ARG, "count = %lld: split R-hat needs at least 4 records "
+                "(two in each half)", (long long)count);
+  const int64_t n = e->n, d = e->d;
+  int64_t K = 0;
+  if (nested_rhat) {
+    if (group < 1) return fail(PBH_ERR_ARG, "group = %d: at least 1 chain per superchain",
+                               (int)group);
+    if (n % group != 0)
+      return fail(PBH_ERR_ARG, "group = %d does not divide the %lld chains", (int)group,
+                  (long long)n);
+    K = n / group;
+    if (K < 2)
+      return fail(PBH_ERR_ARG, "group = %d leaves %lld superchain of %lld chains: nested "
+                  "R-hat needs at least 2", (int)group, (long long)K, (long long)n);
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  // stats [6][d][n], the superchains' (mu, B + W) [2][d][K], the results [2][d]
+  const int64_t n_stats = 6 * d * n, n_sc = 2 * d * K, need = n_stats + n_sc + 2 * d;
+  if (e->rhat_len < need) {
+    e->rhat_len = 0;
+    if (const int rc = dalloc(e->rhat, (size_t)need)) return rc;
+    e->rhat_len = need;
+  }
+  double *stats = e->rhat, *sc = stats + n_stats, *res = sc + n_sc;
+  hipError_t err = pbh::launch_rhat_chain(e->tx, n, (int32_t)d, first, count, stats, e->stream);
+  if (err == hipSuccess && (split_rhat || nested_rhat))
+    err = pbh::launch_rhat_cross(stats, n, (int32_t)d, count, group, sc,
+                                 split_rhat ? res : nullptr, nested_rhat ? res + d : nullptr,
+                                 e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  double host[2 * PBH_MAX_DIM];
+  if (err == hipSuccess && (split_rhat || nested_rhat))
+    err = hipMemcpy(host, res, 2 * d * sizeof(double), hipMemcpyDeviceToHost);
+  if (err == hipSuccess && chain_stats)
+    err = hipMemcpy(chain_stats, stats, n_stats * sizeof(double), hipMemcpyDeviceToHost);
+  if (err != hipSuccess)
+    return fail(PBH_ERR_HIP, "pbh_trace_rhat: %s", hipGetErrorString(err));
+  if (split_rhat) std::memcpy(split_rhat, host, d * sizeof(double));
+  if (nested_rhat) std::memcpy(nested_rhat, host + d, d * sizeof(double));
   return PBH_OK;
 }
 

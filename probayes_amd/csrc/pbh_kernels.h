@@ -244,6 +244,20 @@ hipError_t launch_trace_quantile(const double *tx, const double *tlp, int64_t n,
                                  int32_t d, int64_t first, int32_t count, int32_t nq,
                                  const double *q, int32_t weighted, int32_t lin,
                                  double log_npi, double *out, hipStream_t s);
+// Cross-chain convergence (pbh_rhat.hip).  launch_rhat_chain: stats[6][d][n]
+// = per (chain, dim) mean and variance (ddof 1) of records [first, first + h),
+// [first + count - h, first + count) and the whole window, h = count / 2, from
+// sums shifted by the window's first record; count >= 2 (count < 4 leaves
+// the half variances 0/0).  launch_rhat_cross: split_out [d] (or null) from
+// the 2 n half chains, nested_out [d] (or null) from n / group superchains of
+// `group` consecutive chains, group >= 1, n % group == 0 (sc: 2 d n / group
+// doubles of device scratch, read only with nested_out); everything on the
+// device, a fixed reduction order, no atomics
+hipError_t launch_rhat_chain(const double *tx, int64_t n, int32_t d, int64_t first,
+                             int64_t count, double *stats, hipStream_t s);
+hipError_t launch_rhat_cross(const double *stats, int64_t n, int32_t d, int64_t count,
+                             int64_t group, double *sc, double *split_out,
+                             double *nested_out, hipStream_t s);
 // fft: 2 = the 2 048-point FFT form for count <= 1 536 records with the
 // 4 096-point form for the pairs it cannot decide (list: (d n + 1) / 2 + 1
 // int32 of device scratch), 1 = the 4 096-point form for count <= 2 048

@@ -651,6 +651,30 @@ class Engine:
     res = out.transpose(0, 2, 1).copy()
     return res[0] if scalar else res
 
+  def trace_rhat(self, first=0, count=None, group=None, stats=False):
+    """Cross-chain convergence of trace records [first, first + count), per
+    dim, computed on the device (probayes_amd/diag.py is the definition):
+    {'split': [d], 'nested': [d] or None}.  split: split-R-hat over the 2 N
+    half chains (count >= 4; an odd count drops the middle record).  nested,
+    with group=M: nested R-hat over the N / M superchains of M consecutive
+    chains, which the caller started at one point each (M >= 1 divides N, N /
+    M >= 2).  stats=True adds 'stats': [6, N, d], the per-chain mean and
+    variance (ddof 1) of the first half, the second half and the whole window
+    -- the rows diag.split_rhat / diag.nested_rhat work from."""
+    count = self.trace_len() - first if count is None else count
+    d, n = self.dim, self.n
+    split = np.empty(d)
+    nested = None if group is None else np.empty(d)
+    rows = np.empty((6, d, n)) if stats else None
+    _lib.call('pbh_trace_rhat', self._h, _c.c_int64(int(first)),
+              _c.c_int64(int(count)), _c.c_int32(0 if group is None else int(group)),
+              _dp(split), None if nested is None else _dp(nested),
+              None if rows is None else _dp(rows))
+    res = {'split': split, 'nested': nested}
+    if stats:
+      res['stats'] = rows.transpose(0, 2, 1).copy()
+    return res
+
   def rccl_allreduce_max(self, value):
     v = _c.c_double(float(value))
     _lib.call('pbh_rccl_allreduce_max', self._h, _c.byref(v))

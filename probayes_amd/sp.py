@@ -1385,6 +1385,45 @@ class Sampler:
     res = self._eng.trace_quantile(q, first, count, weighted)
     return {k: res[..., i] for i, k in enumerate(self.names)}
 
+  def trace_rhat(self, first=0, count=None, group=None):
+    """Whether the chains agree, computed by the engine from its device trace
+    (Engine.trace_rhat) without copying the trace to the host: {'split':
+    {name: value}, 'nested': {name: value} or None}.  split is split-R-hat
+    over the 2 N half chains of records [first, first + count) (count >= 4);
+    nested, with group=M, is nested R-hat over the N / M superchains of M
+    consecutive chains (M >= 1 divides N, N / M >= 2; for chains started at
+    one point per superchain).  Covers the sampler's first block while the
+    engine still holds it, as trace_quantile does."""
+    if not self.batched:
+      raise ValueError('trace_rhat needs a batched sampler (chains=N)')
+    if self.spec is not None and self.spec.get('kind') == 'linreg':
+      raise ValueError('trace_rhat: a linreg sampler keeps no engine trace')
+    if self._eng is None:
+      raise ValueError('trace_rhat: the sampler has no engine (no step has '
+                       'run yet, or it was closed)')
+    blk = self._trace_block
+    if blk is None or self._eng_blocks != 1:
+      raise ValueError('trace_rhat: the engine\'s trace is no longer the '
+                       'first block\'s (another block ran, or the chains were '
+                       'rewound or reset)')
+    first = int(first)
+    count = blk.T - first if count is None else int(count)
+    if first < 0 or count < 1 or first + count > blk.T:
+      raise ValueError('trace_rhat: records [{}, {}) outside the block\'s '
+                       '[0, {})'.format(first, first + count, blk.T))
+    if count < 4:
+      raise ValueError('trace_rhat: count = {}: split R-hat needs at least 4 '
+                       'records'.format(count))
+    if group is not None:
+      group, n = int(group), self._eng.n
+      if group < 1 or n % group or n // group < 2:
+        raise ValueError('trace_rhat: group = {} does not split the {} chains '
+                         'into 2 or more superchains of equal size'.format(group, n))
+    res = self._eng.trace_rhat(first, count, group)
+    return {key: None if res[key] is None
+            else {k: float(res[key][i]) for i, k in enumerate(self.names)}
+            for key in ('split', 'nested')}
+
   @staticmethod
   def _runs(steps):
     """(block, record indices) per run of consecutive steps from one block."""
