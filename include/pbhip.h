@@ -31,8 +31,9 @@ extern "C" {
 /* Additions that leave every version-7 call and struct prefix as it was bump
  * the revision: 1 = pbh_model.expr_data / expr_n_obs / expr_n_cols (a caller
  * passes the whole struct, zero-initialised), pbh_eval_expr_data;
- * 2 = pbh_trace_quantile.  pbh_trace_rhat was added within revision 2
- * without a bump: a caller finds it by looking the symbol up.               */
+ * 2 = pbh_trace_quantile.  pbh_trace_rhat and pbh_trace_quantile_pooled were
+ * added within revision 2 without a bump: a caller finds them by looking the
+ * symbol up.                                                                */
 #define PBH_ABI_REVISION 2
 #define PBH_MAX_DIM 32
 
@@ -507,6 +508,26 @@ int pbh_trace_quantile(pbh_engine *eng, int64_t first, int64_t count,
  * generators.                                                               */
 int pbh_trace_rhat(pbh_engine *eng, int64_t first, int64_t count, int32_t group,
                    double *split_rhat, double *nested_rhat, double *chain_stats);
+/* Quantiles of trace records [first, first + count) pooled over every chain
+ * and record, per dim, on the device (added within revision 2 as
+ * pbh_trace_rhat was: look the symbol up).  probayes_amd/diag.py
+ * pooled_quantile is the definition.  Per dim, with s the M = N count values
+ * sorted ascending: vi = (M - 1) q in fp64, lo = floor(vi), hi = min(lo + 1,
+ * M - 1), g = vi - lo, a = s[lo], b = s[hi]; out[j][k] is b - (b - a)(1 - g)
+ * if g >= 0.5, else a + (b - a) g -- np.quantile's default method, bit for
+ * bit.  A dim that holds a NaN gives NaN for every q; there are no other
+ * special cases (a = b = inf gives NaN); -0.0 counts as +0.0 and is returned
+ * as +0.0.  order_stats [nq][2][d] (may be NULL): a and b themselves.
+ * The order statistics are found by a radix select over the monotone 64-bit
+ * image of the doubles in six streaming passes over the window, with integer
+ * histograms as the only state: no record limit, the result equals sorting on
+ * the host whatever the order of the atomics, and two calls give the same
+ * bits.  1 <= count, 1 <= nq <= PBH_QUANTILE_MAX_Q, every q[j] in [0, 1]; out
+ * [nq][d] on the host.  Changes nothing in the engine: not the moments, the
+ * ESS, the trace, the chains or the generators.                             */
+int pbh_trace_quantile_pooled(pbh_engine *eng, int64_t first, int64_t count,
+                              int32_t nq, const double *q, double *out,
+                              double *order_stats);
 
 /* ---- multi-GPU: one RCCL all-gather over xGMI --------- */
 int pbh_rccl_unique_id(uint8_t id[128]);

@@ -985,4 +985,23 @@ __device__ __forceinline__ Decision accept_filter(double lpp, double lp,
   return accept_filter_lead<24>(lpp, lp, t0 >> 8, lin);
 }
 
+// ---------------------------------------------------------------------------
+// The monotone 64-bit image of a double (pbh_quantile.hip sorts by it,
+// pbh_select.hip selects by its digits).
+// ---------------------------------------------------------------------------
+// Orders doubles as unsigned integers: negative values reversed below the
+// positive ones; every NaN is the largest image; -0.0 maps with +0.0.
+__device__ __forceinline__ uint64_t key_image(double v) {
+  if (v != v) return ~0ull;
+  if (v == 0.) v = 0.;
+  const uint64_t u = __builtin_bit_cast(uint64_t, v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+// The double of an image: +0.0 for either zero, one (positive, quiet) NaN for
+// every NaN.
+__device__ __forceinline__ double key_value(uint64_t key) {
+  return __builtin_bit_cast(double, (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key);
+}
+
 }  // namespace pbh

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <algorithm>
 #include <atomic>
@@ -92,6 +93,8 @@ struct pbh_engine {
   int64_t ess_host_len = 0;
   double *rhat = nullptr;        // pbh_trace_rhat's scratch, kept between calls
   int64_t rhat_len = 0;
+  uint64_t *sel = nullptr;       // pbh_trace_quantile_pooled's scratch, likewise
+  int64_t sel_len = 0;
   bool spin_sync = true;     // poll <= 2 ms, then block; PBH_SYNC=block: block
   bool sync_event = false;   // PBH_SYNC=event: poll the last run's end event
   // timing events as marker packets around the launches (default), or
@@ -740,7 +743,7 @@ int pbh_destroy(pbh_engine *e) {
   put(e->msum); put(e->msq); put(e->nacc);
   put(e->gather_send); put(e->gather_recv); put(e->scalar);
   put(e->bm64); put(e->ess); put(e->lgtab); dfree(e->ess_list); put(e->ess_tot);
-  put(e->rhat);
+  put(e->rhat); put(e->sel);
   if (e->ess_host) (void)hipHostFree(e->ess_host);
   if (e->srv_cmd) (void)hipHostFree(e->srv_cmd);
   if (e->srv_done) (void)hipHostFree(e->srv_done);
@@ -2449,6 +2452,80 @@ int pbh_trace_rhat(pbh_engine *e, int64_t first, int64_t count, int32_t group,
     return fail(PBH_ERR_HIP, "pbh_trace_rhat: %s", hipGetErrorString(err));
   if (split_rhat) std::memcpy(split_rhat, host, d * sizeof(double));
   if (nested_rhat) std::memcpy(nested_rhat, host + d, d * sizeof(double));
+  return PBH_OK;
+}
+
+int pbh_trace_quantile_pooled(pbh_engine *e, int64_t first, int64_t count, int32_t nq,
+                              const double *q, double *out, double *order_stats) {
+  if (check_ptr(e, "engine") || check_ptr(q, "q") || check_ptr(out, "out"))
+    return PBH_ERR_ARG;
+  SRV_STOP(e);
+  if (e->cap <= 0 || !e->tx)
+    return fail(PBH_ERR_ARG, "no trace allocated (pbh_alloc_trace first)");
+  if (nq < 1 || nq > PBH_QUANTILE_MAX_Q)
+    return fail(PBH_ERR_ARG, "nq = %d outside 1..%d", (int)nq, PBH_QUANTILE_MAX_Q);
+  for (int32_t j = 0; j < nq; ++j)
+    if (!(q[j] >= 0. && q[j] <= 1.))
+      return fail(PBH_ERR_ARG, "q[%d] = %g is not a quantile in [0, 1]", (int)j, q[j]);
+  if (count < 1) return fail(PBH_ERR_ARG, "count = %lld: at least 1 record", (long long)count);
+  int64_t rec = 0;
+  pbh_trace_len(e, &rec);
+  if (first < 0 || first > rec || count > rec - first)
+    return fail(PBH_ERR_ARG, "trace range [%lld, %lld) outside [0, %lld)",
+                (long long)first, (long long)(first + count), (long long)rec);
+  const int64_t n = e->n, d = e->d, M = n * count;
+  // the two ranks of every quantile, as diag.pooled_quantile places them
+  std::vector<int64_t> lo(nq), hi(nq);
+  std::vector<double> frac(nq);
+  std::vector<uint64_t> ranks;
+  for (int32_t j = 0; j < nq; ++j) {
+    const double vi = (double)(M - 1) * q[j], fl = std::floor(vi);
+    lo[j] = std::min((int64_t)fl, M - 1);
+    hi[j] = std::min(lo[j] + 1, M - 1);
+    frac[j] = vi - fl;
+    ranks.push_back((uint64_t)lo[j]);
+    ranks.push_back((uint64_t)hi[j]);
+  }
+  ranks.push_back((uint64_t)(M - 1));   // the largest element: a NaN if the dim holds one
+  std::sort(ranks.begin(), ranks.end());
+  ranks.erase(std::unique(ranks.begin(), ranks.end()), ranks.end());
+  const int32_t nt = (int32_t)ranks.size();
+  HIP_TRY(hipSetDevice(e->device));
+  const int64_t need = pbh::select_scratch_words((int32_t)d, nt);
+  if (e->sel_len < need) {
+    e->sel_len = 0;
+    if (const int rc = dalloc(e->sel, (size_t)need)) return rc;
+    e->sel_len = need;
+  }
+  std::vector<uint64_t> init((size_t)(4 * d * pbh::kSelectMaxTargets + d));
+  hipError_t err = pbh::launch_select_init(e->sel, (int32_t)d, nt, ranks.data(), init.data(),
+                                           e->stream);
+  for (int32_t pass = 0; err == hipSuccess && pass < pbh::select_passes(); ++pass)
+    err = pbh::launch_select_pass(e->tx, n, (int32_t)d, first, count, e->sel, nt, pass,
+                                  e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  std::vector<double> stats((size_t)(d * nt));   // [d][nt]
+  if (err == hipSuccess)
+    err = hipMemcpy(stats.data(), e->sel + pbh::select_stats_offset((int32_t)d, nt),
+                    stats.size() * sizeof(double), hipMemcpyDeviceToHost);
+  if (err != hipSuccess)
+    return fail(PBH_ERR_HIP, "pbh_trace_quantile_pooled: %s", hipGetErrorString(err));
+  const auto at = [&](int64_t r) {
+    return (int64_t)(std::lower_bound(ranks.begin(), ranks.end(), (uint64_t)r) - ranks.begin());
+  };
+  for (int64_t k = 0; k < d; ++k) {
+    const double *s = stats.data() + k * nt;
+    const bool has_nan = s[nt - 1] != s[nt - 1];
+    for (int32_t j = 0; j < nq; ++j) {
+      const double a = s[at(lo[j])], b = s[at(hi[j])], diff = b - a, g = frac[j];
+      const double v = g >= 0.5 ? b - diff * (1. - g) : a + diff * g;
+      out[j * d + k] = has_nan ? std::numeric_limits<double>::quiet_NaN() : v;
+      if (order_stats) {
+        order_stats[(2 * j) * d + k] = a;
+        order_stats[(2 * j + 1) * d + k] = b;
+      }
+    }
+  }
   return PBH_OK;
 }
 

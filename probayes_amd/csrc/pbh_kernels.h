@@ -258,6 +258,27 @@ hipError_t launch_rhat_chain(const double *tx, int64_t n, int32_t d, int64_t fir
 hipError_t launch_rhat_cross(const double *stats, int64_t n, int32_t d, int64_t count,
                              int64_t group, double *sc, double *split_out,
                              double *nested_out, hipStream_t s);
+// Order statistics of trace records [first, first + count) pooled over chains
+// and records, per dim: a radix select over key_image (pbh_select.hip).  The
+// targets are nt sorted distinct ranks in [0, count n), 1 <= nt <=
+// kSelectMaxTargets (64 quantiles' two ranks each, and the largest element's
+// for the NaN rule).  sc: select_scratch_words(d, nt) 8-byte words of device
+// scratch.  launch_select_init sets every target to the empty prefix and
+// clears the histograms (host: as many words as select_stats_offset minus the
+// histograms, at most 4 d kSelectMaxTargets + d, alive until the stream has
+// been synchronised); launch_select_pass(pass), pass = 0 .. select_passes() -
+// 1 in order, fixes the next digit of every target (two launches).  After the
+// last pass the doubles [d][nt] at sc + select_stats_offset(d, nt) are the
+// order statistics (either zero as +0.0, any NaN as one NaN).
+constexpr int kSelectMaxTargets = 129;
+int64_t select_scratch_words(int32_t d, int32_t nt);
+int64_t select_stats_offset(int32_t d, int32_t nt);
+int32_t select_passes();
+hipError_t launch_select_init(uint64_t *sc, int32_t d, int32_t nt, const uint64_t *ranks,
+                              uint64_t *host, hipStream_t s);
+hipError_t launch_select_pass(const double *tx, int64_t n, int32_t d, int64_t first,
+                              int64_t count, uint64_t *sc, int32_t nt, int32_t pass,
+                              hipStream_t s);
 // fft: 2 = the 2 048-point FFT form for count <= 1 536 records with the
 // 4 096-point form for the pairs it cannot decide (list: (d n + 1) / 2 + 1
 // int32 of device scratch), 1 = the 4 096-point form for count <= 2 048

@@ -39,6 +39,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pbh_device.h"   // key_image
 #include "pbh_kernels.h"
 
 namespace pbh {
@@ -49,15 +50,6 @@ constexpr int kThreads = 64 * kTile;
 constexpr int kMaxP = 2048;              // PBH_QUANTILE_MAX_RECORDS
 constexpr double kTiny = 2.2250738585072014e-308;     // NEARLY_POSITIVE_ZERO
 constexpr double kNpi = 1.7976931348623158e+308;      // NEARLY_POSITIVE_INF
-
-// Orders doubles as unsigned integers: negative values reversed below the
-// positive ones; every NaN is the largest image; -0.0 maps with +0.0.
-__device__ __forceinline__ uint64_t key_image(double v) {
-  if (v != v) return ~0ull;
-  if (v == 0.) v = 0.;
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
 
 // LDS traffic of one wave between two dependent phases: the wave's DS
 // operations complete in order; the fence keeps the compiler from moving

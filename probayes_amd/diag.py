@@ -12,6 +12,9 @@ global chain order (axis 1) and calls the same two functions.
 The values are the IEEE results of the formulas with no special cases: all
 chains constant and equal give NaN (0/0), constant but different +inf, and a
 NaN record propagates.
+
+pooled_quantile is the definition of the posterior quantiles pooled over every
+chain and record (pbh_trace_quantile_pooled, Engine.trace_quantile_pooled).
 """
 import numpy as np
 
@@ -113,3 +116,47 @@ def nested_rhat(moments, count, group):
       b = np.zeros_like(mu)
     bw = b + s2.mean(axis=1)
     return np.sqrt(1. + _var_of_means(mu) / bw.mean(axis=0))
+
+
+def pooled_quantile(x, q, first=0, count=None):
+  """[nq, d]: the quantiles q of a host trace x [N, T, d] over records [first,
+  first + count), pooled over every chain and record, per dim.  With s the M =
+  N count values of a dim sorted ascending: vi = (M - 1) q, lo = floor(vi), hi
+  = min(lo + 1, M - 1), g = vi - lo, a = s[lo], b = s[hi]; the result is b - (b
+  - a) (1 - g) if g >= 0.5, else a + (b - a) g -- np.quantile's default method,
+  written out.  A dim that holds a NaN gives NaN for every q; there are no
+  other special cases (a = b = inf gives inf - inf = NaN), and -0.0 and +0.0
+  are one value."""
+  x = np.asarray(x, float)
+  if x.ndim != 3:
+    raise ValueError('pooled_quantile: a trace [N, T, d], got shape {}'.format(x.shape))
+  first = int(first)
+  count = x.shape[1] - first if count is None else int(count)
+  if count < 1:
+    raise ValueError('pooled_quantile: count = {}: at least 1 record'.format(count))
+  if first < 0 or first + count > x.shape[1]:
+    raise ValueError('pooled_quantile: records [{}, {}) outside [0, {})'.format(
+        first, first + count, x.shape[1]))
+  q = np.atleast_1d(np.asarray(q, float)).ravel()
+  if q.size == 0:
+    raise ValueError('pooled_quantile: no quantile given')
+  if not np.all((q >= 0.) & (q <= 1.)):   # (a NaN fails both comparisons)
+    raise ValueError('pooled_quantile: every q in [0, 1], got {}'.format(q))
+  m = x.shape[0] * count
+  if m < 1:
+    raise ValueError('pooled_quantile: a trace without chains')
+  vi = (m - 1.) * q
+  fl = np.floor(vi)
+  lo = np.minimum(fl.astype(np.int64), m - 1)
+  hi = np.minimum(lo + 1, m - 1)
+  g = vi - fl
+  out = np.empty((q.size, x.shape[2]))
+  for k in range(x.shape[2]):   # a dim at a time: one contiguous copy to sort
+    s = np.sort(x[:, first:first + count, k], axis=None)   # NaN last
+    with np.errstate(invalid='ignore', over='ignore'):
+      a, b = s[lo], s[hi]
+      diff = b - a
+      out[:, k] = np.where(g >= 0.5, b - diff * (1. - g), a + diff * g)
+    if np.isnan(s[-1]):
+      out[:, k] = np.nan
+  return out

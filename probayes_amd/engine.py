@@ -675,6 +675,24 @@ class Engine:
       res['stats'] = rows.transpose(0, 2, 1).copy()
     return res
 
+  def trace_quantile_pooled(self, q, first=0, count=None, order_stats=False):
+    """The quantiles q of trace records [first, first + count) pooled over
+    every chain and record, per dim, computed on the device: [nq, d]
+    (diag.pooled_quantile is the definition; np.quantile's default method, bit
+    for bit).  A radix select in six streaming passes over the window: no
+    record limit.  A dim holding a NaN gives NaN.  nq is at most 64.
+    order_stats=True returns (quantiles, [nq, 2, d]): the two sorted values
+    each quantile is interpolated between."""
+    count = self.trace_len() - first if count is None else count
+    qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, float)).ravel())
+    out = np.empty((max(qs.size, 1), self.dim))
+    stats = np.empty((max(qs.size, 1), 2, self.dim)) if order_stats else None
+    _lib.call('pbh_trace_quantile_pooled', self._h, _c.c_int64(int(first)),
+              _c.c_int64(int(count)), _c.c_int32(qs.size),
+              _dp(qs if qs.size else np.zeros(1)), _dp(out),
+              None if stats is None else _dp(stats))
+    return (out, stats) if order_stats else out
+
   def rccl_allreduce_max(self, value):
     v = _c.c_double(float(value))
     _lib.call('pbh_rccl_allreduce_max', self._h, _c.byref(v))

@@ -1424,6 +1424,33 @@ class Sampler:
             else {k: float(res[key][i]) for i, k in enumerate(self.names)}
             for key in ('split', 'nested')}
 
+  def trace_quantile_pooled(self, q, first=0, count=None):
+    """The posterior quantiles q of every name, pooled over every chain and
+    every record [first, first + count), computed by the engine from its
+    device trace (Engine.trace_quantile_pooled) without copying the trace to
+    the host: {name: [nq]} -- np.quantile of the pooled summary values, bit
+    for bit.  No record limit.  Covers the sampler's first block while the
+    engine still holds it, as trace_quantile does."""
+    if not self.batched:
+      raise ValueError('trace_quantile_pooled needs a batched sampler (chains=N)')
+    if self.spec is not None and self.spec.get('kind') == 'linreg':
+      raise ValueError('trace_quantile_pooled: a linreg sampler keeps no engine trace')
+    if self._eng is None:
+      raise ValueError('trace_quantile_pooled: the sampler has no engine (no step has '
+                       'run yet, or it was closed)')
+    blk = self._trace_block
+    if blk is None or self._eng_blocks != 1:
+      raise ValueError('trace_quantile_pooled: the engine\'s trace is no longer the '
+                       'first block\'s (another block ran, or the chains were '
+                       'rewound or reset)')
+    first = int(first)
+    count = blk.T - first if count is None else int(count)
+    if first < 0 or count < 1 or first + count > blk.T:
+      raise ValueError('trace_quantile_pooled: records [{}, {}) outside the block\'s '
+                       '[0, {})'.format(first, first + count, blk.T))
+    res = self._eng.trace_quantile_pooled(q, first, count)
+    return {k: res[:, i].copy() for i, k in enumerate(self.names)}
+
   @staticmethod
   def _runs(steps):
     """(block, record indices) per run of consecutive steps from one block."""
