@@ -4,15 +4,11 @@
 // The engine owns every device buffer; the caller passes host pointers.
 // Nothing here throws across the C boundary: errors become status codes with
 // a thread-local message (pbh_last_error).
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <string>
 #include <algorithm>
 #include <atomic>
@@ -22,156 +18,17 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/pbhip.h"
-#include "pbh_kernels.h"
+#include "pbh_engine_state.h"
 #include "pbh_expr_host.h"
 #include "pbh_device.h"
 
 using pbh::KArgs;
-
-struct pbh_engine {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  unsigned ev_flags = 0;   // the events' hipEventCreateWithFlags flags
-  // model / proposal / gibbs (device constant blocks)
-  bool has_model = false, has_prop = false, has_gibbs = false;
-  int d = 0;
-  KArgs k{};
-  double *dmodel = nullptr, *dprop = nullptr, *dgibbs = nullptr;
-  std::vector<int32_t> draw_order;  // GAUSS: dim receiving the j-th draw
-  // chains
-  int64_t n = 0, off = 0;
-  double *x = nullptr, *lp = nullptr;
-  bool has_pred = false;
-  int64_t g = 0;  // chain-steps done since pbh_init_chains
-  // randomness
-  int32_t rng = PBH_RNG_PHILOX;
-  uint64_t seed = 0;
-  double *rep = nullptr;
-  int64_t rep_steps = 0, rep_g0 = 0;
-  size_t rep_alloc = 0;          // doubles allocated at rep (device streams reuse it)
-  uint32_t *xo = nullptr;      // xoshiro128** states [4][2][n]
-  bool xo_seeded = false;
-  // legacy NumPy RandomState per chain (pbh_legacy_seed)
-  uint32_t *mt_key = nullptr;
-  bool mt_k4 = true;           // mt_key layout: Mt4's [16][20][n][32] (chunked blocks),
-                               // or the double-buffered [2][624][n] (Mt3)
-  bool legacy_k4 = true;       // PBH_LEGACY_K4=0: the double-buffered state at any chain count
-  bool legacy_fused = true;    // PBH_LEGACY_FUSED=0: pbh_legacy_run as generation + run
-  bool legacy_wp = true;       // PBH_LEGACY_WP=0: the chain-per-lane generator for MH streams
-  bool legacy_ahead = true;    // PBH_LEGACY_AHEAD=0: no twist-ahead pass before fused launches
-  bool mt_odd = false;         // a stream may sit at an odd word (randint drew single words)
-  bool rec_thr = false;        // pbh_set_record_threshold: keep pbh_legacy_run's thresholds
-  double *thr = nullptr;       // [thr_steps][n] thresholds of the last pbh_legacy_run
-  double *ess_tot = nullptr;   // pbh_trace_ess_total's per-dim sums (PBH_MAX_DIM)
-  size_t thr_alloc = 0;
-  int64_t thr_steps = 0;
-  int32_t *mt_pos = nullptr, *mt_has = nullptr, *mt_order = nullptr;
-  double *mt_gauss = nullptr;
-  bool mt_stale = false;       // pbh_restore ran: the streams wait for
-                               // pbh_set_legacy_state (the checkpoint's)
-  // trace
-  int64_t cap = 0;
-  int32_t thin = 1, debug = 0;
-  int64_t rec_base = 0;
-  double *tx = nullptr, *tlp = nullptr, *tpx = nullptr, *tpp = nullptr,
-         *ts = nullptr;
-  uint64_t *tacc = nullptr;
-  // moments (pbh_set_collect)
-  int32_t collect = PBH_COLLECT_MOMENTS;
-  double *msum = nullptr, *msq = nullptr;
-  int64_t *nacc = nullptr;
-  int64_t mom_steps = 0;
-  // production fp64 normal tables (bm64, pbh_device.h), read into LDS
-  double *bm64 = nullptr;
-  double *lgtab = nullptr;     // legacy_log_table (device legacy streams)
-  double *ess = nullptr;     // [d][n] per-chain ESS (pbh_trace_ess), NaN before
-  int32_t *ess_list = nullptr;   // the 2 048-point ESS form's fallback list
-  int64_t ess_list_len = 0;
-  double *ess_host = nullptr;    // pinned staging of the ESS copy-out
-  int64_t ess_host_len = 0;
-  double *rhat = nullptr;        // pbh_trace_rhat's scratch, kept between calls
-  int64_t rhat_len = 0;
-  uint64_t *sel = nullptr;       // pbh_trace_quantile_pooled's scratch, likewise
-  int64_t sel_len = 0;
-  bool spin_sync = true;     // poll <= 2 ms, then block; PBH_SYNC=block: block
-  bool sync_event = false;   // PBH_SYNC=event: poll the last run's end event
-  // timing events as marker packets around the launches (default), or
-  // PBH_EVENT_MARKERS=0: on the first / last dispatch packet
-  // (hipExtLaunchKernel: 2 us less GPU time, 3-4 us more host enqueue and
-  // ~7 us more wall per short launch, measured: profiles/r02j_events.jsonl)
-  bool gmm_full = true;      // PBH_GMM_FULL=0: no steady-state quad kernel
-  bool pair_full = true;     // PBH_PAIR_FULL=0: no steady-state pair kernel
-  int ess_fft = 2;           // PBH_ESS_FFT=1: the 4 096-point form only, 0: direct sums
-  bool iid_full = true;      // PBH_IID_FULL=0: no steady-state iid kernel
-  int fair = 11;             // PBH_FAIR=k: wave priorities alternate every 2^k x 10 ns (0: off)
-  int pair_wg = 512;         // PBH_PAIR_WG=256: FULL pair kernel in 4-wave workgroups
-                             // (512: one table copy per CU, 20-step launches ~5 % faster)
-  // Launches of <= 64 steps (the driver's 20-step shape): the alternation
-  // clock starts at each wave's loop entry and hands over once, half-way
-  // (2^10 ticks = 10.24 us for 20 steps) -- the
-  // free-running clock put the one hand-over anywhere in the launch or nowhere
-  // (profiles/r04f_phase.jsonl: the last wave ends 26.4-29.2 us into a k11
-  // launch, 26.5-26.6 us with the launch-relative clock)
-  int fair_short = 10;       // PBH_FAIR_SHORT=k
-  int fair_rel = 0;          // PBH_FAIR_REL=1: long launches use the relative clock too
-  bool event_markers = true;
-  bool pair_enabled = true;  // PBH_NO_PAIR=1 disables the lane-pair kernel
-  bool gibbs_mfma = true;    // PBH_GIBBS_MFMA=0 keeps the VALU quadratic form
-  bool gibbs_fast = true;    // PBH_GIBBS_FAST=0 keeps the ndtri kernel for Philox
-  int gibbs_lanes = 0;       // PBH_GIBBS_LANES: lanes per chain of that kernel
-  int gmm_lanes = 4;         // PBH_GMM_LANES: lanes per chain of the GMM kernel
-  // MVN target on the host (for the production Gibbs tables)
-  std::vector<double> mvn_mean, mvn_U;
-  double mvn_const = 0.;
-  // production Gibbs: persisted g = P'(x - mu'), Q per chain
-  double *gq = nullptr;
-  // production ufun logs carried as chain state ([d][n], KArgs.lx)
-  double *lx = nullptr;
-  bool lx_valid = false;
-  bool gq_valid = false;
-  // timing of the last pbh_run
-  bool timed = false;
-  int64_t last_launches = 0;
-  // resident sampling server (PBH_SERVER=1; pbh_server_*): the FULL pair
-  // kernel launched once, each eligible pbh_run a command in pinned host
-  // memory; srv_timed: the last run was a command (timed by its stamps)
-  bool srv_enabled = false;
-  bool srv_active = false;
-  bool srv_timed = false;
-  uint32_t srv_seq = 0, srv_pending = 0;
-  int32_t srv_wgs = 0;
-  int64_t srv_idle_ms = 1000;      // PBH_SERVER_IDLE_MS: the kernel's idle exit
-  pbh::SrvCmd *srv_cmd = nullptr;  // pinned, fine-grained
-  pbh::SrvDone *srv_done = nullptr;
-  pbh::SrvCmd *srv_mail = nullptr;   // the device mailbox the workgroups poll
-  int32_t srv_done_len = 0;
-  // the command protocol (KArgs.srv_mode): 1 direct (the default) --
-  // srv_mail is fine-grained device memory the host writes through srv_wmail
-  // (its host mapping) and every workgroup polls; 0 relay -- workgroup 0
-  // polls the pinned host block srv_cmd and copies each command into
-  // srv_mail.  Direct needs a host mapping whose stores the device sees: the
-  // first launch probes it (srv_probed) and falls back to the relay.
-  int32_t srv_mode = 1;
-  bool srv_probed = false;
-  bool srv_mail_fine = false;        // srv_mail came from the fine-grained pool
-  pbh::SrvCmd *srv_wmail = nullptr;
-  // srv_last: the last submit (or launch) -- never moved forward at a wait:
-  // a command completes after its submit, and each workgroup's idle timer
-  // starts at its completion, so idle measured from the submit is an upper
-  // bound on the kernel's own
-  std::chrono::steady_clock::time_point srv_last{};
-  // a server command was lost (the kernel ended or hung before completing
-  // it): the chain state may be partly advanced, so runs refuse until
-  // pbh_init_chains / pbh_restore / pbh_set_chains replace it
-  bool state_lost = false;
-  int64_t srv_commands = 0, srv_launches = 0;
-  // RCCL
-  ncclComm_t comm = nullptr;
-  int32_t rank = 0, world = 1;
-  double *gather_send = nullptr, *gather_recv = nullptr, *scalar = nullptr;
-};
+using pbh::check_ptr;
+using pbh::dalloc;
+using pbh::dfree;
+using pbh::dretire;
+using pbh::fail;
+using pbh::srv_stop;
 
 namespace {
 
@@ -184,23 +41,6 @@ int64_t mt_words(bool k4) { return k4 ? 16 * 20 * 32 : 2 * 624; }
 int64_t mt_state_words(bool k4) { return k4 ? 20 * 32 : mt_words(k4); }
 
 thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                        \
-  do {                                                                       \
-    hipError_t _e = (expr);                                                  \
-    if (_e != hipSuccess)                                                    \
-      return fail(PBH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
 
 #define RCCL_TRY(expr)                                                       \
   do {                                                                       \
@@ -272,73 +112,64 @@ int cache_release_all() {
   return freed;
 }
 
-template <class T>
-void dfree(T *&p) {
-  if (p) {
-    ResCache &c = res_cache();
+}  // namespace
+
+int pbh::fail(int code, const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+
+int pbh::dmem(DMem op, void **p, size_t bytes) {
+  ResCache &c = res_cache();
+  if (void *v = *p) {
+    *p = nullptr;
+    bool kept = false;
     {
       std::lock_guard<std::mutex> lk(c.mu);
-      c.live.erase(static_cast<void *>(p));
+      auto it = c.live.find(v);
+      if (op == DMem::Retire && it != c.live.end() && c.idle_bytes + it->second <= c.cap) {
+        c.idle.emplace(std::make_pair(cur_device(), it->second), v);
+        c.idle_bytes += it->second;
+        kept = true;
+      }
+      if (it != c.live.end()) c.live.erase(it);
     }
-    (void)hipFree(p);
+    if (!kept) (void)hipFree(v);
   }
-  p = nullptr;
-}
-
-// a buffer of a destroyed engine (its stream drained): into the cache while
-// it fits, else freed
-template <class T>
-void dretire(T *&p) {
-  if (!p) return;
-  ResCache &c = res_cache();
-  void *v = static_cast<void *>(p);
-  p = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(c.mu);
-    auto it = c.live.find(v);
-    if (it != c.live.end() && c.idle_bytes + it->second <= c.cap) {
-      c.idle.emplace(std::make_pair(cur_device(), it->second), v);
-      c.idle_bytes += it->second;
-      c.live.erase(it);
-      return;
-    }
-    if (it != c.live.end()) c.live.erase(it);
-  }
-  (void)hipFree(v);
-}
-
-template <class T>
-int dalloc(T *&p, size_t count) {
-  dfree(p);
-  if (count == 0) return PBH_OK;
-  const size_t bytes = count * sizeof(T);
-  ResCache &c = res_cache();
+  if (op != DMem::Alloc || bytes == 0) return PBH_OK;
   {
     std::lock_guard<std::mutex> lk(c.mu);
     auto it = c.idle.find(std::make_pair(cur_device(), bytes));
     if (it != c.idle.end()) {
-      p = static_cast<T *>(it->second);
+      *p = it->second;
       c.idle.erase(it);
       c.idle_bytes -= bytes;
-      c.live.emplace(static_cast<void *>(p), bytes);
+      c.live.emplace(*p, bytes);
       ++c.hits;
       return PBH_OK;
     }
     ++c.misses;
   }
-  hipError_t err = hipMalloc((void **)&p, bytes);
+  hipError_t err = hipMalloc(p, bytes);
   if (err == hipErrorOutOfMemory && cache_release_all() > 0) {
     (void)hipGetLastError();
-    err = hipMalloc((void **)&p, bytes);
+    err = hipMalloc(p, bytes);
   }
   if (err != hipSuccess) {
-    p = nullptr;
+    *p = nullptr;
     return fail(PBH_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(err));
   }
   std::lock_guard<std::mutex> lk(c.mu);
-  c.live.emplace(static_cast<void *>(p), bytes);
+  c.live.emplace(*p, bytes);
   return PBH_OK;
 }
+
+namespace {
 
 int upload(double *&dst, const std::vector<double> &h, hipStream_t s) {
   int rc = dalloc(dst, h.size() ? h.size() : 1);
@@ -355,10 +186,6 @@ size_t pack(std::vector<double> &blk, const double *a, int64_t n) {
   const size_t o = blk.size();
   for (int64_t i = 0; i < n; ++i) blk.push_back(a[i]);
   return o;
-}
-
-int check_ptr(const void *p, const char *name) {
-  return p ? PBH_OK : fail(PBH_ERR_ARG, "%s must not be NULL", name);
 }
 
 // init [n][d] (the caller's row-major chains) -> x [d][n]
@@ -382,8 +209,6 @@ void free_trace(pbh_engine *e) {
 }
 
 }  // namespace
-
-extern "C" {
 
 // ---------------------------------------------------------------------------
 // Resident sampling server (PBH_SERVER=1, bench.py's default): the FULL pair
@@ -454,27 +279,6 @@ void srv_write(pbh_engine *e, uint32_t n, uint64_t arg, uint32_t q) {
   cmd->arg = arg;
   __atomic_store_n(&cmd->seq, q, __ATOMIC_RELEASE);
   if (e->srv_mode & 1) __builtin_ia32_sfence();   // out of any write-combining buffer
-}
-
-int srv_stop(pbh_engine *e) {
-  if (!e->srv_active) return PBH_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = PBH_OK;
-  if (e->srv_pending) {
-    rc = srv_wait(e, e->srv_pending, false);
-    e->srv_pending = 0;
-  }
-  if (!srv_kernel_ended(e)) {
-    const uint32_t q = ++e->srv_seq;
-    srv_write(e, 0u, pbh::srv_arg(0, 0u, 0u, pbh::kSrvExit, q), q);
-    const int rc2 = srv_wait(e, q, true);
-    if (!rc) rc = rc2;
-  }
-  const hipError_t err = hipStreamSynchronize(e->stream);
-  e->srv_active = false;
-  if (!rc && err != hipSuccess)
-    rc = fail(PBH_ERR_HIP, "sampling server exit: %s", hipGetErrorString(err));
-  return rc;
 }
 
 // the fine-grained device mailbox and the host's mapping of it (direct)
@@ -601,13 +405,28 @@ void srv_submit(pbh_engine *e, int64_t n_steps, int32_t fair, int32_t fair_rel) 
 }
 }  // namespace
 
-#define SRV_STOP(e)                        \
-  do {                                     \
-    if ((e)->srv_active) {                 \
-      const int srv_rc_ = srv_stop(e);     \
-      if (srv_rc_) return srv_rc_;         \
-    }                                      \
-  } while (0)
+int pbh::srv_stop(pbh_engine *e) {
+  if (!e->srv_active) return PBH_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = PBH_OK;
+  if (e->srv_pending) {
+    rc = srv_wait(e, e->srv_pending, false);
+    e->srv_pending = 0;
+  }
+  if (!srv_kernel_ended(e)) {
+    const uint32_t q = ++e->srv_seq;
+    srv_write(e, 0u, pbh::srv_arg(0, 0u, 0u, pbh::kSrvExit, q), q);
+    const int rc2 = srv_wait(e, q, true);
+    if (!rc) rc = rc2;
+  }
+  const hipError_t err = hipStreamSynchronize(e->stream);
+  e->srv_active = false;
+  if (!rc && err != hipSuccess)
+    rc = fail(PBH_ERR_HIP, "sampling server exit: %s", hipGetErrorString(err));
+  return rc;
+}
+
+extern "C" {
 
 
 const char *pbh_last_error(void) { return g_err.c_str(); }
@@ -742,8 +561,8 @@ int pbh_destroy(pbh_engine *e) {
   e->cap = 0;
   put(e->msum); put(e->msq); put(e->nacc);
   put(e->gather_send); put(e->gather_recv); put(e->scalar);
-  put(e->bm64); put(e->ess); put(e->lgtab); dfree(e->ess_list); put(e->ess_tot);
-  put(e->rhat); put(e->sel);
+  put(e->bm64); put(e->ess); put(e->lgtab); put(e->ess_list); put(e->ess_tot);
+  put(e->scratch);
   if (e->ess_host) (void)hipHostFree(e->ess_host);
   if (e->srv_cmd) (void)hipHostFree(e->srv_cmd);
   if (e->srv_done) (void)hipHostFree(e->srv_done);
@@ -1953,20 +1772,6 @@ int pbh_legacy_draws(pbh_engine *e, int64_t n_steps, int64_t step0, int32_t kind
   return PBH_OK;
 }
 
-// The engine stream's completion, as pbh_sync waits for it: polled for up to
-// 2 ms (PBH_SYNC, spin_sync), then a blocking wait.  A blocking
-// hipStreamSynchronize wakes ~10-50 us after a short kernel ends.
-static hipError_t stream_wait(pbh_engine *e) {
-  if (!e->spin_sync) return hipStreamSynchronize(e->stream);
-  const auto t0 = std::chrono::steady_clock::now();
-  hipError_t q;
-  while ((q = hipStreamQuery(e->stream)) == hipErrorNotReady) {
-    if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(2000))
-      return hipStreamSynchronize(e->stream);
-  }
-  return q;
-}
-
 int pbh_sync(pbh_engine *e) {
   if (check_ptr(e, "engine")) return PBH_ERR_ARG;
   if (e->srv_active) {   // never the stream: the server kernel is on it
@@ -2261,38 +2066,6 @@ int pbh_set_legacy_state(pbh_engine *e, const uint32_t *key, const int32_t *pos,
   return PBH_OK;
 }
 
-int pbh_trace_len(pbh_engine *e, int64_t *n_recorded) {
-  if (check_ptr(e, "engine") || check_ptr(n_recorded, "n_recorded")) return PBH_ERR_ARG;
-  const int64_t r = e->cap > 0 ? e->g / e->thin - e->rec_base : 0;
-  *n_recorded = std::max<int64_t>(0, std::min(r, e->cap));
-  return PBH_OK;
-}
-
-int pbh_get_trace(pbh_engine *e, int64_t first, int64_t cnt, double *x,
-                  double *logp, uint64_t *acc, double *p_x, double *p_p,
-                  double *s) {
-  if (check_ptr(e, "engine")) return PBH_ERR_ARG;
-  SRV_STOP(e);
-  int64_t rec = 0;
-  pbh_trace_len(e, &rec);
-  if (first < 0 || cnt < 0 || first + cnt > rec)
-    return fail(PBH_ERR_ARG, "trace range [%lld, %lld) outside [0, %lld)",
-                (long long)first, (long long)(first + cnt), (long long)rec);
-  if ((p_x || p_p || s) && !e->debug)
-    return fail(PBH_ERR_STATE, "debug trace not allocated");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const size_t n = e->n, d = e->d, W = (e->n + 63) / 64;
-  if (cnt == 0) return PBH_OK;
-  if (x) HIP_TRY(hipMemcpy(x, e->tx + first * d * n, cnt * d * n * sizeof(double), hipMemcpyDeviceToHost));
-  if (logp) HIP_TRY(hipMemcpy(logp, e->tlp + first * n, cnt * n * sizeof(double), hipMemcpyDeviceToHost));
-  if (acc) HIP_TRY(hipMemcpy(acc, e->tacc + first * W, cnt * W * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  if (p_x) HIP_TRY(hipMemcpy(p_x, e->tpx + first * d * n, cnt * d * n * sizeof(double), hipMemcpyDeviceToHost));
-  if (p_p) HIP_TRY(hipMemcpy(p_p, e->tpp + first * n, cnt * n * sizeof(double), hipMemcpyDeviceToHost));
-  if (s) HIP_TRY(hipMemcpy(s, e->ts + first * n, cnt * n * sizeof(double), hipMemcpyDeviceToHost));
-  return PBH_OK;
-}
-
 int pbh_get_moments(pbh_engine *e, double *sum, double *sumsq, int64_t *n_acc,
                     int64_t *n_steps) {
   if (check_ptr(e, "engine")) return PBH_ERR_ARG;
@@ -2305,287 +2078,6 @@ int pbh_get_moments(pbh_engine *e, double *sum, double *sumsq, int64_t *n_acc,
   if (sumsq) HIP_TRY(hipMemcpy(sumsq, e->msq, dn * sizeof(double), hipMemcpyDeviceToHost));
   if (n_acc) HIP_TRY(hipMemcpy(n_acc, e->nacc, e->n * sizeof(int64_t), hipMemcpyDeviceToHost));
   if (n_steps) *n_steps = e->mom_steps;
-  return PBH_OK;
-}
-
-int pbh_trace_stats(pbh_engine *e, int64_t first, int64_t count, double *sum,
-                    double *sumsq, int64_t *n_acc) {
-  if (check_ptr(e, "engine")) return PBH_ERR_ARG;
-  SRV_STOP(e);
-  int64_t rec = 0;
-  pbh_trace_len(e, &rec);
-  if (first < 0 || count < 0 || first + count > rec)
-    return fail(PBH_ERR_ARG, "trace range [%lld, %lld) outside [0, %lld)",
-                (long long)first, (long long)(first + count), (long long)rec);
-  HIP_TRY(hipSetDevice(e->device));
-  const int64_t n = e->n, W = (n + 63) / 64;
-  HIP_TRY(pbh::launch_trace_stats(e->tx, e->tacc, n, e->d, W, first, count,
-                                  e->msum, e->msq, e->nacc, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  e->mom_steps = count;
-  const size_t dn = (size_t)e->d * n;
-  if (sum) HIP_TRY(hipMemcpy(sum, e->msum, dn * sizeof(double), hipMemcpyDeviceToHost));
-  if (sumsq) HIP_TRY(hipMemcpy(sumsq, e->msq, dn * sizeof(double), hipMemcpyDeviceToHost));
-  if (n_acc) HIP_TRY(hipMemcpy(n_acc, e->nacc, n * sizeof(int64_t), hipMemcpyDeviceToHost));
-  return PBH_OK;
-}
-
-int pbh_trace_expectation(pbh_engine *e, int64_t first, int64_t count,
-                          double exponent, double *out) {
-  if (check_ptr(e, "engine") || check_ptr(out, "out")) return PBH_ERR_ARG;
-  SRV_STOP(e);
-  int64_t rec = 0;
-  pbh_trace_len(e, &rec);
-  if (first < 0 || count < 1 || first + count > rec)
-    return fail(PBH_ERR_ARG, "trace range [%lld, %lld) outside [0, %lld)",
-                (long long)first, (long long)(first + count), (long long)rec);
-  if (!std::isfinite(exponent)) return fail(PBH_ERR_ARG, "exponent must be finite");
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t dn = (size_t)e->d * e->n;
-  double *dout = nullptr;
-  HIP_TRY(hipMalloc(&dout, dn * sizeof(double)));
-  hipError_t err = pbh::launch_trace_expectation(
-      e->tx, e->tlp, e->n, e->d, first, count, exponent,
-      e->k.pscale == PBH_PSCALE_LIN ? 1 : 0, e->k.log_npi, dout, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  if (err == hipSuccess)
-    err = hipMemcpy(out, dout, dn * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dout);
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_trace_expectation: %s", hipGetErrorString(err));
-  return PBH_OK;
-}
-
-int pbh_trace_quantile(pbh_engine *e, int64_t first, int64_t count, int32_t nq,
-                       const double *q, int32_t weighted, double *out) {
-  if (check_ptr(e, "engine") || check_ptr(q, "q") || check_ptr(out, "out"))
-    return PBH_ERR_ARG;
-  SRV_STOP(e);
-  if (e->cap <= 0 || !e->tx || !e->tlp)
-    return fail(PBH_ERR_ARG, "no trace allocated (pbh_alloc_trace first)");
-  if (nq < 1 || nq > PBH_QUANTILE_MAX_Q)
-    return fail(PBH_ERR_ARG, "nq = %d outside 1..%d", (int)nq, PBH_QUANTILE_MAX_Q);
-  for (int32_t j = 0; j < nq; ++j)
-    if (!(q[j] >= 0. && q[j] <= 1.))
-      return fail(PBH_ERR_ARG, "q[%d] = %g is not a quantile in [0, 1]", (int)j, q[j]);
-  if (count < 1) return fail(PBH_ERR_ARG, "count = %lld: at least 1 record", (long long)count);
-  if (count > PBH_QUANTILE_MAX_RECORDS)
-    return fail(PBH_ERR_ARG, "count = %lld above the %d records a series is sorted at",
-                (long long)count, PBH_QUANTILE_MAX_RECORDS);
-  int64_t rec = 0;
-  pbh_trace_len(e, &rec);
-  if (first < 0 || first > rec || count > rec - first)
-    return fail(PBH_ERR_ARG, "trace range [%lld, %lld) outside [0, %lld)",
-                (long long)first, (long long)(first + count), (long long)rec);
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t res = (size_t)nq * e->d * e->n;
-  double *dbuf = nullptr;   // q [nq], then the result [nq][d][n]
-  HIP_TRY(hipMalloc(&dbuf, (PBH_QUANTILE_MAX_Q + res) * sizeof(double)));
-  hipError_t err = hipMemcpyAsync(dbuf, q, nq * sizeof(double), hipMemcpyHostToDevice,
-                                  e->stream);
-  if (err == hipSuccess)
-    err = pbh::launch_trace_quantile(e->tx, e->tlp, e->n, e->d, first, (int32_t)count, nq,
-                                     dbuf, weighted ? 1 : 0,
-                                     e->k.pscale == PBH_PSCALE_LIN ? 1 : 0, e->k.log_npi,
-                                     dbuf + PBH_QUANTILE_MAX_Q, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  if (err == hipSuccess)
-    err = hipMemcpy(out, dbuf + PBH_QUANTILE_MAX_Q, res * sizeof(double),
-                    hipMemcpyDeviceToHost);
-  (void)hipFree(dbuf);
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_trace_quantile: %s", hipGetErrorString(err));
-  return PBH_OK;
-}
-
-int pbh_trace_rhat(pbh_engine *e, int64_t first, int64_t count, int32_t group,
-                   double *split_rhat, double *nested_rhat, double *chain_stats) {
-  if (check_ptr(e, "engine")) return PBH_ERR_ARG;
-  SRV_STOP(e);
-  if (e->cap <= 0 || !e->tx)
-    return fail(PBH_ERR_ARG, "no trace allocated (pbh_alloc_trace first)");
-  int64_t rec = 0;
-  pbh_trace_len(e, &rec);
-  if (first < 0 || first > rec || count < 0 || count > rec - first)
-    return fail(PBH_ERR_ARG, "trace range [%lld, %lld) outside [0, %lld)",
-                (long long)first, (long long)(first + count), (long long)rec);
-  if (count < 2)
-    return fail(PBH_ERR_ARG, "count = %lld: a variance needs at least 2 records",
-                (long long)count);
-  if (split_rhat && count < 4)
-    return fail(PBH_ERR_ARG, "count = %lld: split R-hat needs at least 4 records "
-                "(two in each half)", (long long)count);
-  const int64_t n = e->n, d = e->d;
-  int64_t K = 0;
-  if (nested_rhat) {
-    if (group < 1) return fail(PBH_ERR_ARG, "group = %d: at least 1 chain per superchain",
-                               (int)group);
-    if (n % group != 0)
-      return fail(PBH_ERR_ARG, "group = %d does not divide the %lld chains", (int)group,
-                  (long long)n);
-    K = n / group;
-    if (K < 2)
-      return fail(PBH_ERR_ARG, "group = %d leaves %lld superchain of %lld chains: nested "
-                  "R-hat needs at least 2", (int)group, (long long)K, (long long)n);
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  // stats [6][d][n], the superchains' (mu, B + W) [2][d][K], the results [2][d]
-  const int64_t n_stats = 6 * d * n, n_sc = 2 * d * K, need = n_stats + n_sc + 2 * d;
-  if (e->rhat_len < need) {
-    e->rhat_len = 0;
-    if (const int rc = dalloc(e->rhat, (size_t)need)) return rc;
-    e->rhat_len = need;
-  }
-  double *stats = e->rhat, *sc = stats + n_stats, *res = sc + n_sc;
-  hipError_t err = pbh::launch_rhat_chain(e->tx, n, (int32_t)d, first, count, stats, e->stream);
-  if (err == hipSuccess && (split_rhat || nested_rhat))
-    err = pbh::launch_rhat_cross(stats, n, (int32_t)d, count, group, sc,
-                                 split_rhat ? res : nullptr, nested_rhat ? res + d : nullptr,
-                                 e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  double host[2 * PBH_MAX_DIM];
-  if (err == hipSuccess && (split_rhat || nested_rhat))
-    err = hipMemcpy(host, res, 2 * d * sizeof(double), hipMemcpyDeviceToHost);
-  if (err == hipSuccess && chain_stats)
-    err = hipMemcpy(chain_stats, stats, n_stats * sizeof(double), hipMemcpyDeviceToHost);
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_trace_rhat: %s", hipGetErrorString(err));
-  if (split_rhat) std::memcpy(split_rhat, host, d * sizeof(double));
-  if (nested_rhat) std::memcpy(nested_rhat, host + d, d * sizeof(double));
-  return PBH_OK;
-}
-
-int pbh_trace_quantile_pooled(pbh_engine *e, int64_t first, int64_t count, int32_t nq,
-                              const double *q, double *out, double *order_stats) {
-  if (check_ptr(e, "engine") || check_ptr(q, "q") || check_ptr(out, "out"))
-    return PBH_ERR_ARG;
-  SRV_STOP(e);
-  if (e->cap <= 0 || !e->tx)
-    return fail(PBH_ERR_ARG, "no trace allocated (pbh_alloc_trace first)");
-  if (nq < 1 || nq > PBH_QUANTILE_MAX_Q)
-    return fail(PBH_ERR_ARG, "nq = %d outside 1..%d", (int)nq, PBH_QUANTILE_MAX_Q);
-  for (int32_t j = 0; j < nq; ++j)
-    if (!(q[j] >= 0. && q[j] <= 1.))
-      return fail(PBH_ERR_ARG, "q[%d] = %g is not a quantile in [0, 1]", (int)j, q[j]);
-  if (count < 1) return fail(PBH_ERR_ARG, "count = %lld: at least 1 record", (long long)count);
-  int64_t rec = 0;
-  pbh_trace_len(e, &rec);
-  if (first < 0 || first > rec || count > rec - first)
-    return fail(PBH_ERR_ARG, "trace range [%lld, %lld) outside [0, %lld)",
-                (long long)first, (long long)(first + count), (long long)rec);
-  const int64_t n = e->n, d = e->d, M = n * count;
-  // the two ranks of every quantile, as diag.pooled_quantile places them
-  std::vector<int64_t> lo(nq), hi(nq);
-  std::vector<double> frac(nq);
-  std::vector<uint64_t> ranks;
-  for (int32_t j = 0; j < nq; ++j) {
-    const double vi = (double)(M - 1) * q[j], fl = std::floor(vi);
-    lo[j] = std::min((int64_t)fl, M - 1);
-    hi[j] = std::min(lo[j] + 1, M - 1);
-    frac[j] = vi - fl;
-    ranks.push_back((uint64_t)lo[j]);
-    ranks.push_back((uint64_t)hi[j]);
-  }
-  ranks.push_back((uint64_t)(M - 1));   // the largest element: a NaN if the dim holds one
-  std::sort(ranks.begin(), ranks.end());
-  ranks.erase(std::unique(ranks.begin(), ranks.end()), ranks.end());
-  const int32_t nt = (int32_t)ranks.size();
-  HIP_TRY(hipSetDevice(e->device));
-  const int64_t need = pbh::select_scratch_words((int32_t)d, nt);
-  if (e->sel_len < need) {
-    e->sel_len = 0;
-    if (const int rc = dalloc(e->sel, (size_t)need)) return rc;
-    e->sel_len = need;
-  }
-  std::vector<uint64_t> init((size_t)(4 * d * pbh::kSelectMaxTargets + d));
-  hipError_t err = pbh::launch_select_init(e->sel, (int32_t)d, nt, ranks.data(), init.data(),
-                                           e->stream);
-  for (int32_t pass = 0; err == hipSuccess && pass < pbh::select_passes(); ++pass)
-    err = pbh::launch_select_pass(e->tx, n, (int32_t)d, first, count, e->sel, nt, pass,
-                                  e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  std::vector<double> stats((size_t)(d * nt));   // [d][nt]
-  if (err == hipSuccess)
-    err = hipMemcpy(stats.data(), e->sel + pbh::select_stats_offset((int32_t)d, nt),
-                    stats.size() * sizeof(double), hipMemcpyDeviceToHost);
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_trace_quantile_pooled: %s", hipGetErrorString(err));
-  const auto at = [&](int64_t r) {
-    return (int64_t)(std::lower_bound(ranks.begin(), ranks.end(), (uint64_t)r) - ranks.begin());
-  };
-  for (int64_t k = 0; k < d; ++k) {
-    const double *s = stats.data() + k * nt;
-    const bool has_nan = s[nt - 1] != s[nt - 1];
-    for (int32_t j = 0; j < nq; ++j) {
-      const double a = s[at(lo[j])], b = s[at(hi[j])], diff = b - a, g = frac[j];
-      const double v = g >= 0.5 ? b - diff * (1. - g) : a + diff * g;
-      out[j * d + k] = has_nan ? std::numeric_limits<double>::quiet_NaN() : v;
-      if (order_stats) {
-        order_stats[(2 * j) * d + k] = a;
-        order_stats[(2 * j + 1) * d + k] = b;
-      }
-    }
-  }
-  return PBH_OK;
-}
-
-int pbh_trace_ess(pbh_engine *e, int64_t first, int64_t count, double *ess) {
-  if (check_ptr(e, "engine")) return PBH_ERR_ARG;
-  SRV_STOP(e);
-  int64_t rec = 0;
-  pbh_trace_len(e, &rec);
-  if (first < 0 || count < 2 || first + count > rec)
-    return fail(PBH_ERR_ARG, "ESS needs >= 2 records inside [0, %lld), got [%lld, %lld)",
-                (long long)rec, (long long)first, (long long)(first + count));
-  HIP_TRY(hipSetDevice(e->device));
-  const int64_t dn = (int64_t)e->d * e->n;
-  if (e->ess_fft >= 2 && e->ess_list_len < (dn + 1) / 2 + 1) {
-    dfree(e->ess_list);
-    e->ess_list_len = 0;
-    HIP_TRY(hipMalloc(&e->ess_list, ((dn + 1) / 2 + 1) * sizeof(int32_t)));
-    e->ess_list_len = (dn + 1) / 2 + 1;
-  }
-  HIP_TRY(pbh::launch_trace_ess(e->tx, e->n, e->d, first, count, e->ess, e->stream,
-                                e->ess_fft, e->ess_list));
-  if (ess) {
-    // through a pinned staging buffer: a pageable copy of the 512 KB cfg5
-    // result was ~0.1 ms of the call
-    if (e->ess_host_len < dn) {
-      if (e->ess_host) (void)hipHostFree(e->ess_host);
-      e->ess_host = nullptr;
-      e->ess_host_len = 0;
-      HIP_TRY(hipHostMalloc(&e->ess_host, dn * sizeof(double), hipHostMallocDefault));
-      e->ess_host_len = dn;
-    }
-    HIP_TRY(hipMemcpyAsync(e->ess_host, e->ess, dn * sizeof(double), hipMemcpyDeviceToHost,
-                           e->stream));
-    HIP_TRY(stream_wait(e));
-    std::memcpy(ess, e->ess_host, dn * sizeof(double));
-  }
-  return PBH_OK;
-}
-
-int pbh_trace_ess_total(pbh_engine *e, int64_t first, int64_t count, double *total) {
-  if (check_ptr(e, "engine") || check_ptr(total, "total")) return PBH_ERR_ARG;
-  // the per-chain ESS on the device (no copy), then the per-dim sums
-  if (const int rc = pbh_trace_ess(e, first, count, nullptr)) return rc;
-  const int d = e->d;
-  if (!e->ess_host || e->ess_host_len < d) {
-    if (e->ess_host) (void)hipHostFree(e->ess_host);
-    e->ess_host = nullptr;
-    e->ess_host_len = 0;
-    HIP_TRY(hipHostMalloc(&e->ess_host, d * sizeof(double), hipHostMallocDefault));
-    e->ess_host_len = d;
-  }
-  // the totals land in the scalar scratch (d doubles, allocated lazily)
-  if (!e->ess_tot) {
-    if (const int rc = dalloc(e->ess_tot, PBH_MAX_DIM)) return rc;
-  }
-  HIP_TRY(pbh::launch_ess_total(e->ess, e->n, d, e->ess_tot, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->ess_host, e->ess_tot, d * sizeof(double), hipMemcpyDeviceToHost,
-                         e->stream));
-  HIP_TRY(stream_wait(e));
-  std::memcpy(total, e->ess_host, d * sizeof(double));
   return PBH_OK;
 }
 

@@ -1,0 +1,285 @@
+// pbh_trace.cpp -- the trace entry points of include/pbhip.h: the recorded
+// trace copied out, and the reductions over it that run on the device.  No
+// kernel lives here: the launches are pbh_kernels.h's, the host arithmetic
+// pbh_trace_host.h's.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <initializer_list>
+
+#include "pbh_engine_state.h"
+#include "pbh_trace_host.h"
+
+using pbh::check_ptr;
+using pbh::fail;
+
+namespace {
+
+struct NamedPtr {
+  const void *p;
+  const char *name;
+};
+
+// what a refused window says, of (first, end, rec)
+constexpr char kRange[] = "trace range [%lld, %lld) outside [0, %lld)";
+constexpr char kRangeEss[] = "ESS needs >= 2 records inside [0, %3$lld), got [%1$lld, %2$lld)";
+
+// The preamble of a trace entry point, in the order the ABI reports things:
+// the engine and the caller's pointers `ptrs` are not null, the resident server
+// is stopped, with need_trace a trace is allocated, `own` (the entry point's
+// argument checks that come before the window's; a status) passes, and records
+// [first, first + count) with count >= min_count lie inside the recorded ones.
+template <class Own = int (*)()>
+int trace_enter(pbh_engine *e, std::initializer_list<NamedPtr> ptrs, bool need_trace,
+                int64_t first, int64_t count, int64_t min_count,
+                Own own = [] { return PBH_OK; }, const char *range = kRange) {
+  if (check_ptr(e, "engine")) return PBH_ERR_ARG;
+  for (const NamedPtr &np : ptrs)
+    if (check_ptr(np.p, np.name)) return PBH_ERR_ARG;
+  SRV_STOP(e);
+  if (need_trace && (e->cap <= 0 || !e->tx || !e->tlp))
+    return fail(PBH_ERR_ARG, "no trace allocated (pbh_alloc_trace first)");
+  if (const int rc = own()) return rc;
+  int64_t rec = 0;
+  pbh_trace_len(e, &rec);
+  if (!pbh::trace_window_ok(rec, first, count, min_count))
+    return fail(PBH_ERR_ARG, range, (long long)first,
+                (long long)pbh::trace_window_end(first, count), (long long)rec);
+  return PBH_OK;
+}
+
+// the checks of a quantile list and of its window's least count
+int quantile_args(int32_t nq, const double *q, int64_t count) {
+  const std::string bad = pbh::quantile_list_error(nq, q);
+  if (!bad.empty()) return fail(PBH_ERR_ARG, "%s", bad.c_str());
+  if (count < 1) return fail(PBH_ERR_ARG, "count = %lld: at least 1 record", (long long)count);
+  return PBH_OK;
+}
+
+// the reduction scratch at `bytes` or more
+int scratch(pbh_engine *e, size_t bytes) {
+  return pbh::dgrow(e->scratch, e->scratch_bytes, bytes);
+}
+
+// the pinned staging buffer at n doubles or more
+int ess_host(pbh_engine *e, size_t n) {
+  if (e->ess_host_len >= n) return PBH_OK;
+  if (e->ess_host) (void)hipHostFree(e->ess_host);
+  e->ess_host = nullptr;
+  e->ess_host_len = 0;
+  HIP_TRY(hipHostMalloc(&e->ess_host, n * sizeof(double), hipHostMallocDefault));
+  e->ess_host_len = n;
+  return PBH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbh_trace_len(pbh_engine *e, int64_t *n_recorded) {
+  if (check_ptr(e, "engine") || check_ptr(n_recorded, "n_recorded")) return PBH_ERR_ARG;
+  const int64_t r = e->cap > 0 ? e->g / e->thin - e->rec_base : 0;
+  *n_recorded = std::max<int64_t>(0, std::min(r, e->cap));
+  return PBH_OK;
+}
+
+int pbh_get_trace(pbh_engine *e, int64_t first, int64_t cnt, double *x,
+                  double *logp, uint64_t *acc, double *p_x, double *p_p,
+                  double *s) {
+  if (const int rc = trace_enter(e, {}, false, first, cnt, 0)) return rc;
+  if ((p_x || p_p || s) && !e->debug)
+    return fail(PBH_ERR_STATE, "debug trace not allocated");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t n = e->n, d = e->d, W = (e->n + 63) / 64;
+  if (cnt == 0) return PBH_OK;
+  if (x) HIP_TRY(hipMemcpy(x, e->tx + first * d * n, cnt * d * n * sizeof(double), hipMemcpyDeviceToHost));
+  if (logp) HIP_TRY(hipMemcpy(logp, e->tlp + first * n, cnt * n * sizeof(double), hipMemcpyDeviceToHost));
+  if (acc) HIP_TRY(hipMemcpy(acc, e->tacc + first * W, cnt * W * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (p_x) HIP_TRY(hipMemcpy(p_x, e->tpx + first * d * n, cnt * d * n * sizeof(double), hipMemcpyDeviceToHost));
+  if (p_p) HIP_TRY(hipMemcpy(p_p, e->tpp + first * n, cnt * n * sizeof(double), hipMemcpyDeviceToHost));
+  if (s) HIP_TRY(hipMemcpy(s, e->ts + first * n, cnt * n * sizeof(double), hipMemcpyDeviceToHost));
+  return PBH_OK;
+}
+
+int pbh_trace_stats(pbh_engine *e, int64_t first, int64_t count, double *sum,
+                    double *sumsq, int64_t *n_acc) {
+  if (const int rc = trace_enter(e, {}, false, first, count, 0)) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  const int64_t n = e->n, W = (n + 63) / 64;
+  HIP_TRY(pbh::launch_trace_stats(e->tx, e->tacc, n, e->d, W, first, count,
+                                  e->msum, e->msq, e->nacc, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->mom_steps = count;
+  const size_t dn = (size_t)e->d * n;
+  if (sum) HIP_TRY(hipMemcpy(sum, e->msum, dn * sizeof(double), hipMemcpyDeviceToHost));
+  if (sumsq) HIP_TRY(hipMemcpy(sumsq, e->msq, dn * sizeof(double), hipMemcpyDeviceToHost));
+  if (n_acc) HIP_TRY(hipMemcpy(n_acc, e->nacc, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  return PBH_OK;
+}
+
+int pbh_trace_expectation(pbh_engine *e, int64_t first, int64_t count,
+                          double exponent, double *out) {
+  if (const int rc = trace_enter(e, {{out, "out"}}, false, first, count, 1)) return rc;
+  if (!std::isfinite(exponent)) return fail(PBH_ERR_ARG, "exponent must be finite");
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t dn = (size_t)e->d * e->n;
+  if (const int rc = scratch(e, dn * sizeof(double))) return rc;
+  double *dout = reinterpret_cast<double *>(e->scratch);
+  hipError_t err = pbh::launch_trace_expectation(
+      e->tx, e->tlp, e->n, e->d, first, count, exponent,
+      e->k.pscale == PBH_PSCALE_LIN ? 1 : 0, e->k.log_npi, dout, e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess)
+    err = hipMemcpy(out, dout, dn * sizeof(double), hipMemcpyDeviceToHost);
+  if (err != hipSuccess)
+    return fail(PBH_ERR_HIP, "pbh_trace_expectation: %s", hipGetErrorString(err));
+  return PBH_OK;
+}
+
+int pbh_trace_quantile(pbh_engine *e, int64_t first, int64_t count, int32_t nq,
+                       const double *q, int32_t weighted, double *out) {
+  const auto own = [&] {
+    if (const int rc = quantile_args(nq, q, count)) return rc;
+    if (count > PBH_QUANTILE_MAX_RECORDS)
+      return fail(PBH_ERR_ARG, "count = %lld above the %d records a series is sorted at",
+                  (long long)count, PBH_QUANTILE_MAX_RECORDS);
+    return PBH_OK;
+  };
+  if (const int rc = trace_enter(e, {{q, "q"}, {out, "out"}}, true, first, count, 1, own))
+    return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t res = (size_t)nq * e->d * e->n;
+  if (const int rc = scratch(e, (PBH_QUANTILE_MAX_Q + res) * sizeof(double))) return rc;
+  double *dbuf = reinterpret_cast<double *>(e->scratch);   // q [nq], then the result [nq][d][n]
+  hipError_t err = hipMemcpyAsync(dbuf, q, nq * sizeof(double), hipMemcpyHostToDevice,
+                                  e->stream);
+  if (err == hipSuccess)
+    err = pbh::launch_trace_quantile(e->tx, e->tlp, e->n, e->d, first, (int32_t)count, nq,
+                                     dbuf, weighted ? 1 : 0,
+                                     e->k.pscale == PBH_PSCALE_LIN ? 1 : 0, e->k.log_npi,
+                                     dbuf + PBH_QUANTILE_MAX_Q, e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess)
+    err = hipMemcpy(out, dbuf + PBH_QUANTILE_MAX_Q, res * sizeof(double),
+                    hipMemcpyDeviceToHost);
+  if (err != hipSuccess)
+    return fail(PBH_ERR_HIP, "pbh_trace_quantile: %s", hipGetErrorString(err));
+  return PBH_OK;
+}
+
+int pbh_trace_rhat(pbh_engine *e, int64_t first, int64_t count, int32_t group,
+                   double *split_rhat, double *nested_rhat, double *chain_stats) {
+  if (const int rc = trace_enter(e, {}, true, first, count, 0)) return rc;
+  if (count < 2)
+    return fail(PBH_ERR_ARG, "count = %lld: a variance needs at least 2 records",
+                (long long)count);
+  if (split_rhat && count < 4)
+    return fail(PBH_ERR_ARG, "count = %lld: split R-hat needs at least 4 records "
+                "(two in each half)", (long long)count);
+  const int64_t n = e->n, d = e->d;
+  int64_t K = 0;
+  if (nested_rhat) {
+    if (group < 1) return fail(PBH_ERR_ARG, "group = %d: at least 1 chain per superchain",
+                               (int)group);
+    if (n % group != 0)
+      return fail(PBH_ERR_ARG, "group = %d does not divide the %lld chains", (int)group,
+                  (long long)n);
+    K = n / group;
+    if (K < 2)
+      return fail(PBH_ERR_ARG, "group = %d leaves %lld superchain of %lld chains: nested "
+                  "R-hat needs at least 2", (int)group, (long long)K, (long long)n);
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  // stats [6][d][n], the superchains' (mu, B + W) [2][d][K], the results [2][d]
+  const int64_t n_stats = 6 * d * n, n_sc = 2 * d * K, need = n_stats + n_sc + 2 * d;
+  if (const int rc = scratch(e, (size_t)need * sizeof(double))) return rc;
+  double *stats = reinterpret_cast<double *>(e->scratch), *sc = stats + n_stats,
+         *res = sc + n_sc;
+  hipError_t err = pbh::launch_rhat_chain(e->tx, n, (int32_t)d, first, count, stats, e->stream);
+  if (err == hipSuccess && (split_rhat || nested_rhat))
+    err = pbh::launch_rhat_cross(stats, n, (int32_t)d, count, group, sc,
+                                 split_rhat ? res : nullptr, nested_rhat ? res + d : nullptr,
+                                 e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  double host[2 * PBH_MAX_DIM];
+  if (err == hipSuccess && (split_rhat || nested_rhat))
+    err = hipMemcpy(host, res, 2 * d * sizeof(double), hipMemcpyDeviceToHost);
+  if (err == hipSuccess && chain_stats)
+    err = hipMemcpy(chain_stats, stats, n_stats * sizeof(double), hipMemcpyDeviceToHost);
+  if (err != hipSuccess)
+    return fail(PBH_ERR_HIP, "pbh_trace_rhat: %s", hipGetErrorString(err));
+  if (split_rhat) std::memcpy(split_rhat, host, d * sizeof(double));
+  if (nested_rhat) std::memcpy(nested_rhat, host + d, d * sizeof(double));
+  return PBH_OK;
+}
+
+int pbh_trace_quantile_pooled(pbh_engine *e, int64_t first, int64_t count, int32_t nq,
+                              const double *q, double *out, double *order_stats) {
+  if (const int rc = trace_enter(e, {{q, "q"}, {out, "out"}}, true, first, count, 1,
+                                 [&] { return quantile_args(nq, q, count); }))
+    return rc;
+  const int64_t n = e->n, d = e->d;
+  const pbh::PooledPlan plan = pbh::pooled_plan(n * count, nq, q);
+  const int32_t nt = (int32_t)plan.ranks.size();
+  HIP_TRY(hipSetDevice(e->device));
+  if (const int rc = scratch(e, (size_t)pbh::select_scratch_words((int32_t)d, nt) *
+                                    sizeof(uint64_t)))
+    return rc;
+  uint64_t *sel = reinterpret_cast<uint64_t *>(e->scratch);
+  std::vector<uint64_t> init((size_t)(4 * d * pbh::kSelectMaxTargets + d));
+  hipError_t err = pbh::launch_select_init(sel, (int32_t)d, nt, plan.ranks.data(), init.data(),
+                                           e->stream);
+  for (int32_t pass = 0; err == hipSuccess && pass < pbh::select_passes(); ++pass)
+    err = pbh::launch_select_pass(e->tx, n, (int32_t)d, first, count, sel, nt, pass, e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  std::vector<double> stats((size_t)(d * nt));   // [d][nt]
+  if (err == hipSuccess)
+    err = hipMemcpy(stats.data(), sel + pbh::select_stats_offset((int32_t)d, nt),
+                    stats.size() * sizeof(double), hipMemcpyDeviceToHost);
+  if (err != hipSuccess)
+    return fail(PBH_ERR_HIP, "pbh_trace_quantile_pooled: %s", hipGetErrorString(err));
+  pbh::pooled_interpolate(plan, d, stats.data(), out, order_stats);
+  return PBH_OK;
+}
+
+int pbh_trace_ess(pbh_engine *e, int64_t first, int64_t count, double *ess) {
+  if (const int rc = trace_enter(e, {}, false, first, count, 2, [] { return PBH_OK; }, kRangeEss))
+    return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t dn = (size_t)e->d * e->n;
+  if (e->ess_fft >= 2)
+    if (const int rc = pbh::dgrow(e->ess_list, e->ess_list_len, (dn + 1) / 2 + 1)) return rc;
+  HIP_TRY(pbh::launch_trace_ess(e->tx, e->n, e->d, first, count, e->ess, e->stream,
+                                e->ess_fft, e->ess_list));
+  if (ess) {
+    // through a pinned staging buffer: a pageable copy of the 512 KB cfg5
+    // result was ~0.1 ms of the call
+    if (const int rc = ess_host(e, dn)) return rc;
+    HIP_TRY(hipMemcpyAsync(e->ess_host, e->ess, dn * sizeof(double), hipMemcpyDeviceToHost,
+                           e->stream));
+    HIP_TRY(pbh::stream_wait(e));
+    std::memcpy(ess, e->ess_host, dn * sizeof(double));
+  }
+  return PBH_OK;
+}
+
+int pbh_trace_ess_total(pbh_engine *e, int64_t first, int64_t count, double *total) {
+  if (check_ptr(e, "engine") || check_ptr(total, "total")) return PBH_ERR_ARG;
+  // the per-chain ESS on the device (no copy), then the per-dim sums
+  if (const int rc = pbh_trace_ess(e, first, count, nullptr)) return rc;
+  const int d = e->d;
+  if (const int rc = ess_host(e, d)) return rc;
+  // the totals land in the scalar scratch (d doubles, allocated lazily)
+  if (!e->ess_tot) {
+    if (const int rc = pbh::dalloc(e->ess_tot, PBH_MAX_DIM)) return rc;
+  }
+  HIP_TRY(pbh::launch_ess_total(e->ess, e->n, d, e->ess_tot, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->ess_host, e->ess_tot, d * sizeof(double), hipMemcpyDeviceToHost,
+                         e->stream));
+  HIP_TRY(pbh::stream_wait(e));
+  std::memcpy(total, e->ess_host, d * sizeof(double));
+  return PBH_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,41 @@
+// pbh_trace_host.h -- the host arithmetic of the trace reductions: the window
+// check every trace entry point makes, the checks of a quantile list, and the
+// host steps of the pooled quantile around the device's radix select.  No HIP:
+// a host compiler alone builds it (tests/trace_host_main.cpp).  Built with
+// -ffp-contract=off: the interpolation must round as NumPy's does.
+#pragma once
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+namespace pbh {
+
+// Whether records [first, first + count) lie inside [0, rec) with count >=
+// min_count (rec >= 0): no sum is formed, so no argument overflows.
+bool trace_window_ok(int64_t rec, int64_t first, int64_t count, int64_t min_count);
+// first + count for the message of a refused window, saturated at the ends of
+// int64 where the sum leaves it.
+int64_t trace_window_end(int64_t first, int64_t count);
+
+// What is wrong with the quantiles q[0..nq) (nq in 1..PBH_QUANTILE_MAX_Q,
+// every q[j] in [0, 1]; a NaN is not), or empty.
+std::string quantile_list_error(int32_t nq, const double *q);
+
+// The pooled quantiles q[0..nq) of M values, as diag.pooled_quantile places
+// them: vi = (M - 1) q, lo = floor(vi), hi = min(lo + 1, M - 1), frac = vi - lo.
+// ranks: the order statistics the device selects -- every lo and hi and M - 1
+// (the largest element: a NaN if the dim holds one), sorted and distinct.
+struct PooledPlan {
+  std::vector<int64_t> lo, hi;
+  std::vector<double> frac;
+  std::vector<uint64_t> ranks;
+};
+PooledPlan pooled_plan(int64_t M, int32_t nq, const double *q);
+// stats [d][nt], the values at p.ranks per dim -> out [nq][d], and with
+// order_stats [nq][2][d] the two values each quantile is interpolated
+// between.  A dim whose largest element is a NaN gives NaN for every q.
+void pooled_interpolate(const PooledPlan &p, int64_t d, const double *stats, double *out,
+                        double *order_stats);
+
+}  // namespace pbh

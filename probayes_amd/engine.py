@@ -38,6 +38,13 @@ def _i32(a):
   return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _quantiles(q):
+  """q as the C-ABI takes it: (a contiguous float64 array, nq).  An empty q
+  is (one zero nobody reads, 0): the library refuses nq = 0 itself."""
+  qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, float)).ravel())
+  return (qs, qs.size) if qs.size else (np.zeros(1), 0)
+
+
 def condcov_tables(mean, cov, lo, hi):
   """CondCov.__init__ (cond_cov.py:22-39): per coordinate i the regression
   row Sigma_{i,-i} Sigma_{-i,-i}^{-1}, the Schur sd and the cdf limits of the
@@ -527,10 +534,14 @@ class Engine:
     _lib.call('pbh_trace_len', self._h, _c.byref(r))
     return r.value
 
+  def _window(self, first, count):
+    """(first, count), count defaulting to every record from first on."""
+    return first, self.trace_len() - first if count is None else count
+
   def trace(self, first=0, count=None, debug=None):
     """Recorded steps as chain-major arrays shaped like the golden fixtures:
     v_x [N, T, d], v_p [N, T], u [N, T] (uint8); with debug also p_x, p_p, s."""
-    count = self.trace_len() - first if count is None else count
+    first, count = self._window(first, count)
     n, d = self.n, self.dim
     W = (n + 63) // 64
     x = np.empty((count, d, n))
@@ -564,7 +575,7 @@ class Engine:
   def trace_stats(self, first=0, count=None):
     """Per-chain sum / sumsq / n_acc of trace records [first, first +
     count), reduced on the device (also replaces the engine's moments)."""
-    count = self.trace_len() - first if count is None else count
+    first, count = self._window(first, count)
     n, d = self.n, self.dim
     s = np.empty((d, n))
     q = np.empty((d, n))
@@ -607,7 +618,7 @@ class Engine:
   def trace_ess(self, first=0, count=None):
     """Per-chain, per-dim initial-positive-sequence ESS of trace records
     [first, first + count), computed on the device: [N, d]."""
-    count = self.trace_len() - first if count is None else count
+    first, count = self._window(first, count)
     out = np.empty((self.dim, self.n))
     _lib.call('pbh_trace_ess', self._h, _c.c_int64(int(first)),
               _c.c_int64(int(count)), _dp(out))
@@ -616,7 +627,7 @@ class Engine:
   def trace_ess_total(self, first=0, count=None):
     """Per dim, the sum over chains of trace_ess (reduced on the device):
     [d]."""
-    count = self.trace_len() - first if count is None else count
+    first, count = self._window(first, count)
     out = np.empty(self.dim)
     _lib.call('pbh_trace_ess_total', self._h, _c.c_int64(int(first)),
               _c.c_int64(int(count)), _dp(out))
@@ -626,7 +637,7 @@ class Engine:
     """PD.expectation (pd.py:373-405) of the summary of trace records
     [first, first + count), computed on the device: [N, d] of
     sum p v^exponent / sum p with p the recorded prob rescaled to linear."""
-    count = self.trace_len() - first if count is None else count
+    first, count = self._window(first, count)
     out = np.empty((self.dim, self.n))
     _lib.call('pbh_trace_expectation', self._h, _c.c_int64(int(first)),
               _c.c_int64(int(count)), _c.c_double(float(exponent or 0.)),
@@ -640,14 +651,13 @@ class Engine:
     itself.  weighted: the recorded prob rescaled to linear as weights;
     otherwise unit weights (the empirical quantile).  count is at most 2 048
     records (PBH_QUANTILE_MAX_RECORDS), nq at most 64."""
-    count = self.trace_len() - first if count is None else count
+    first, count = self._window(first, count)
     scalar = np.isscalar(q)
-    qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, float)).ravel())
-    out = np.empty((max(qs.size, 1), self.dim, self.n))
+    qs, nq = _quantiles(q)
+    out = np.empty((qs.size, self.dim, self.n))
     _lib.call('pbh_trace_quantile', self._h, _c.c_int64(int(first)),
-              _c.c_int64(int(count)), _c.c_int32(qs.size),
-              _dp(qs if qs.size else np.zeros(1)), _c.c_int32(1 if weighted else 0),
-              _dp(out))
+              _c.c_int64(int(count)), _c.c_int32(nq), _dp(qs),
+              _c.c_int32(1 if weighted else 0), _dp(out))
     res = out.transpose(0, 2, 1).copy()
     return res[0] if scalar else res
 
@@ -661,7 +671,7 @@ class Engine:
     M >= 2).  stats=True adds 'stats': [6, N, d], the per-chain mean and
     variance (ddof 1) of the first half, the second half and the whole window
     -- the rows diag.split_rhat / diag.nested_rhat work from."""
-    count = self.trace_len() - first if count is None else count
+    first, count = self._window(first, count)
     d, n = self.dim, self.n
     split = np.empty(d)
     nested = None if group is None else np.empty(d)
@@ -683,13 +693,12 @@ class Engine:
     record limit.  A dim holding a NaN gives NaN.  nq is at most 64.
     order_stats=True returns (quantiles, [nq, 2, d]): the two sorted values
     each quantile is interpolated between."""
-    count = self.trace_len() - first if count is None else count
-    qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, float)).ravel())
-    out = np.empty((max(qs.size, 1), self.dim))
-    stats = np.empty((max(qs.size, 1), 2, self.dim)) if order_stats else None
+    first, count = self._window(first, count)
+    qs, nq = _quantiles(q)
+    out = np.empty((qs.size, self.dim))
+    stats = np.empty((qs.size, 2, self.dim)) if order_stats else None
     _lib.call('pbh_trace_quantile_pooled', self._h, _c.c_int64(int(first)),
-              _c.c_int64(int(count)), _c.c_int32(qs.size),
-              _dp(qs if qs.size else np.zeros(1)), _dp(out),
+              _c.c_int64(int(count)), _c.c_int32(nq), _dp(qs), _dp(out),
               None if stats is None else _dp(stats))
     return (out, stats) if order_stats else out
 

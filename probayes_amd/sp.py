@@ -1356,6 +1356,30 @@ class Sampler:
     self._cur, self._j = None, 0
 
   # ---- summaries -------------------------------------------------------------
+  def _device_window(self, what, first, count, min_count=1):
+    """The guards of a reduction `what` over the engine's device trace: a
+    batched sampler that is not linreg, with an engine whose trace is still
+    the first block's, and records [first, first + count) inside that block
+    (count defaults to the rest of it).  Returns (first, count)."""
+    if not self.batched:
+      raise ValueError('{} needs a batched sampler (chains=N)'.format(what))
+    if self.spec is not None and self.spec.get('kind') == 'linreg':
+      raise ValueError('{}: a linreg sampler keeps no engine trace'.format(what))
+    if self._eng is None:
+      raise ValueError('{}: the sampler has no engine (no step has '
+                       'run yet, or it was closed)'.format(what))
+    blk = self._trace_block
+    if blk is None or self._eng_blocks != 1:
+      raise ValueError('{}: the engine\'s trace is no longer the '
+                       'first block\'s (another block ran, or the chains were '
+                       'rewound or reset)'.format(what))
+    first = int(first)
+    count = blk.T - first if count is None else int(count)
+    if first < 0 or count < min_count or first + count > blk.T:
+      raise ValueError('{}: records [{}, {}) outside the block\'s '
+                       '[0, {})'.format(what, first, first + count, blk.T))
+    return first, count
+
   def trace_quantile(self, q, first=0, count=None, weighted=True):
     """summary.v.sorted(name).quantile(q)[name] for every name and chain,
     computed by the engine from its device trace (Engine.trace_quantile)
@@ -1365,23 +1389,7 @@ class Sampler:
     that block is all T steps, and the result is SP(samples).v.sorted(name)
     .quantile(q)[name] chain by chain.  weighted=False takes unit weights
     instead of v.prob.  At most 2 048 records."""
-    if not self.batched:
-      raise ValueError('trace_quantile needs a batched sampler (chains=N)')
-    if self.spec is not None and self.spec.get('kind') == 'linreg':
-      raise ValueError('trace_quantile: a linreg sampler keeps no engine trace')
-    if self._eng is None:
-      raise ValueError('trace_quantile: the sampler has no engine (no step has '
-                       'run yet, or it was closed)')
-    blk = self._trace_block
-    if blk is None or self._eng_blocks != 1:
-      raise ValueError('trace_quantile: the engine\'s trace is no longer the '
-                       'first block\'s (another block ran, or the chains were '
-                       'rewound or reset)')
-    first = int(first)
-    count = blk.T - first if count is None else int(count)
-    if first < 0 or count < 1 or first + count > blk.T:
-      raise ValueError('trace_quantile: records [{}, {}) outside the block\'s '
-                       '[0, {})'.format(first, first + count, blk.T))
+    first, count = self._device_window('trace_quantile', first, count)
     res = self._eng.trace_quantile(q, first, count, weighted)
     return {k: res[..., i] for i, k in enumerate(self.names)}
 
@@ -1394,23 +1402,7 @@ class Sampler:
     consecutive chains (M >= 1 divides N, N / M >= 2; for chains started at
     one point per superchain).  Covers the sampler's first block while the
     engine still holds it, as trace_quantile does."""
-    if not self.batched:
-      raise ValueError('trace_rhat needs a batched sampler (chains=N)')
-    if self.spec is not None and self.spec.get('kind') == 'linreg':
-      raise ValueError('trace_rhat: a linreg sampler keeps no engine trace')
-    if self._eng is None:
-      raise ValueError('trace_rhat: the sampler has no engine (no step has '
-                       'run yet, or it was closed)')
-    blk = self._trace_block
-    if blk is None or self._eng_blocks != 1:
-      raise ValueError('trace_rhat: the engine\'s trace is no longer the '
-                       'first block\'s (another block ran, or the chains were '
-                       'rewound or reset)')
-    first = int(first)
-    count = blk.T - first if count is None else int(count)
-    if first < 0 or count < 1 or first + count > blk.T:
-      raise ValueError('trace_rhat: records [{}, {}) outside the block\'s '
-                       '[0, {})'.format(first, first + count, blk.T))
+    first, count = self._device_window('trace_rhat', first, count)
     if count < 4:
       raise ValueError('trace_rhat: count = {}: split R-hat needs at least 4 '
                        'records'.format(count))
@@ -1431,23 +1423,7 @@ class Sampler:
     the host: {name: [nq]} -- np.quantile of the pooled summary values, bit
     for bit.  No record limit.  Covers the sampler's first block while the
     engine still holds it, as trace_quantile does."""
-    if not self.batched:
-      raise ValueError('trace_quantile_pooled needs a batched sampler (chains=N)')
-    if self.spec is not None and self.spec.get('kind') == 'linreg':
-      raise ValueError('trace_quantile_pooled: a linreg sampler keeps no engine trace')
-    if self._eng is None:
-      raise ValueError('trace_quantile_pooled: the sampler has no engine (no step has '
-                       'run yet, or it was closed)')
-    blk = self._trace_block
-    if blk is None or self._eng_blocks != 1:
-      raise ValueError('trace_quantile_pooled: the engine\'s trace is no longer the '
-                       'first block\'s (another block ran, or the chains were '
-                       'rewound or reset)')
-    first = int(first)
-    count = blk.T - first if count is None else int(count)
-    if first < 0 or count < 1 or first + count > blk.T:
-      raise ValueError('trace_quantile_pooled: records [{}, {}) outside the block\'s '
-                       '[0, {})'.format(first, first + count, blk.T))
+    first, count = self._device_window('trace_quantile_pooled', first, count)
     res = self._eng.trace_quantile_pooled(q, first, count)
     return {k: res[:, i].copy() for i, k in enumerate(self.names)}
 

@@ -31,6 +31,7 @@ import oracle
 from oracle.workloads import golden_init
 from probayes_amd import diag
 from probayes_amd._lib import PbhError
+from trace_helpers import check_no_side_effects, run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -42,16 +43,6 @@ Q64 = list(np.linspace(0., 1., 64))
 QSETS = {'qs': QS, 'one': [.5], 'q64': Q64}
 N_BIG, T_BIG = 2004, 160
 WINDOWS = [(40, 120), (40, 119), (0, 1)]
-
-
-def _run(spec, init, t, seed=3):
-  from probayes_amd import Engine
-  eng = Engine(spec)
-  eng.init_chains(init)
-  eng.set_rng('philox', seed=seed)
-  eng.alloc_trace(t, 1)
-  eng.run(t, steps_per_launch=64)
-  return eng
 
 
 def _order_stats(x, q, first, count):
@@ -77,7 +68,7 @@ def _big(name):
   """One run per model: the host copy of the trace and every device result,
   each asked for twice."""
   spec = oracle.golden_spec(name)
-  eng = _run(spec, golden_init(name, N_BIG), T_BIG)
+  eng = run(spec, golden_init(name, N_BIG), T_BIG)
   try:
     x = eng.trace()['v_x']
     dev, again = {}, {}
@@ -115,7 +106,7 @@ def test_two_calls_give_the_same_bits(name):
 @pytest.mark.parametrize('name', ['diag10', 'gmm2'])
 def test_few_chains(name):
   spec = oracle.golden_spec(name)
-  eng = _run(spec, golden_init(name, 67), 40)
+  eng = run(spec, golden_init(name, 67), 40)
   try:
     x = eng.trace()['v_x']
     for key, q in QSETS.items():
@@ -126,7 +117,7 @@ def test_few_chains(name):
     assert np.array_equal(whole, diag.pooled_quantile(x, [.5]))
   finally:
     eng.close()
-  eng = _run(spec, golden_init(name, 1), 1)
+  eng = run(spec, golden_init(name, 1), 1)
   try:
     x = eng.trace()['v_x']
     assert x.shape == (1, 1, spec['dim'])
@@ -166,7 +157,7 @@ def test_ties_and_every_digit(kind):
   base = oracle.golden_spec('gmm2')
   spec = dict(base, proposal=dict(base['proposal'], scale=np.zeros(2)))
   x0 = _tied_starts(kind)
-  eng = _run(spec, x0, 12)
+  eng = run(spec, x0, 12)
   try:
     x = eng.trace()['v_x']
     assert x.shape == (130, 12, 2) and (x == x0[:, None, :]).all()   # the chains did not move
@@ -190,7 +181,7 @@ def test_a_nan_chain_makes_its_dim_nan():
   spec = dict(base, proposal=dict(base['proposal'], scale=np.zeros(2)))
   x0 = np.repeat(np.array([[-1., 0.5], [0.25, 2.], [3., -1.]]), 2, axis=0)
   x0[4, 1] = np.nan
-  eng = _run(spec, x0, 12)
+  eng = run(spec, x0, 12)
   try:
     x = eng.trace()['v_x']
     assert np.array_equal(x, np.broadcast_to(x0[:, None, :], x.shape), equal_nan=True)
@@ -208,7 +199,7 @@ def test_many_chains():
   dim in the count kernel, each flushing its LDS histogram, and a tail after
   the unrolled rounds."""
   n, t = 33000, 8
-  eng = _run(oracle.golden_spec('gmm2'), golden_init('gmm2', n), t)
+  eng = run(oracle.golden_spec('gmm2'), golden_init('gmm2', n), t)
   try:
     x = eng.trace()['v_x']
     dev = {key: eng.trace_quantile_pooled(q, 0, t, order_stats=True) for key, q in QSETS.items()}
@@ -221,43 +212,11 @@ def test_many_chains():
 
 
 def test_no_side_effects():
-  from probayes_amd import Engine
-
-  def start():
-    eng = Engine(oracle.golden_spec('gmm2'))
-    eng.init_chains(golden_init('gmm2', 516))
-    eng.set_rng('philox', seed=9)
-    eng.alloc_trace(96, 1)
-    eng.run(64, steps_per_launch=64)
-    return eng
-
-  eng, ref = start(), start()
-  try:
-    st0 = eng.trace_stats(0, 64)
-    ess0 = eng.trace_ess(0, 64).copy()
-    tr0, mom0, x0 = eng.trace(0, 64), eng.moments(), eng.state()
+  def reduce(eng):
     eng.trace_quantile_pooled(QS, 3, 61)
     eng.trace_quantile_pooled(Q64, 0, 64, order_stats=True)
-    tr1, mom1, x1 = eng.trace(0, 64), eng.moments(), eng.state()
-    for k in ('v_x', 'v_p', 'u'):
-      assert np.array_equal(tr0[k], tr1[k]), k
-    for k in ('sum', 'sumsq', 'n_acc'):
-      assert np.array_equal(mom0[k], mom1[k]), k
-    assert mom0['n_steps'] == mom1['n_steps']
-    assert np.array_equal(x0[0], x1[0]) and np.array_equal(x0[1], x1[1])
-    st1 = eng.trace_stats(0, 64)
-    for k in ('sum', 'sumsq', 'n_acc'):
-      assert np.array_equal(st0[k], st1[k]), k
-    assert np.array_equal(ess0, eng.trace_ess(0, 64))
-    # the run continues as it does without the calls
-    eng.run(32, steps_per_launch=64)
-    ref.run(32, steps_per_launch=64)
-    ta, tb = eng.trace(), ref.trace()
-    for k in ('v_x', 'v_p', 'u'):
-      assert np.array_equal(ta[k], tb[k]), k
-  finally:
-    eng.close()
-    ref.close()
+
+  check_no_side_effects(reduce, 516)
 
 
 def test_refusals_leave_the_engine_working():

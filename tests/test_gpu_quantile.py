@@ -19,6 +19,7 @@ from oracle.workloads import golden_init
 from probayes_amd._lib import PbhError
 from probayes_amd.pd import PD
 from probayes_amd.pscales import rescale
+from trace_helpers import check_no_side_effects, run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -26,17 +27,6 @@ sys.path.insert(0, ROOT)
 pytestmark = pytest.mark.gpu
 
 QS = [0., 0.05, 0.5, 0.95, 1.]
-
-
-def _run(name, n, t, seed=3):
-  from probayes_amd import Engine
-  spec = oracle.golden_spec(name)
-  eng = Engine(spec)
-  eng.init_chains(golden_init(name, n))
-  eng.set_rng('philox', seed=seed)
-  eng.alloc_trace(t, 1)
-  eng.run(t, steps_per_launch=64)
-  return spec, eng
 
 
 def _host(vals, prob, pscale, qs):
@@ -89,7 +79,8 @@ N_BIG, T_BIG, FIRST_BIG = 2003, 160, 40
 def _big(name):
   """One run per model shared by the unweighted and the weighted test: the
   host trace and both device results."""
-  spec, eng = _run(name, N_BIG, T_BIG)
+  spec = oracle.golden_spec(name)
+  eng = run(spec, golden_init(name, N_BIG), T_BIG)
   try:
     tr = eng.trace()
     cnt = T_BIG - FIRST_BIG
@@ -140,7 +131,8 @@ EDGES = [(1, 0), (1, 2047), (2, 5), (3, 2045), (64, 0), (65, 1983), (1024, 1024)
 
 
 def test_record_count_edges():
-  spec, eng = _run('gmm2', 67, 2048)
+  spec = oracle.golden_spec('gmm2')
+  eng = run(spec, golden_init('gmm2', 67), 2048)
   try:
     tr = eng.trace()
     for cnt, first in EDGES:
@@ -188,50 +180,14 @@ def test_refusals_leave_the_engine_working():
 
 
 def test_no_side_effects_and_determinism():
-  from probayes_amd import Engine
-
-  def start():
-    spec = oracle.golden_spec('gmm2')
-    eng = Engine(spec)
-    eng.init_chains(golden_init('gmm2', 515))
-    eng.set_rng('philox', seed=9)
-    eng.alloc_trace(96, 1)
-    eng.run(64, steps_per_launch=64)
-    return eng
-
-  eng, ref = start(), start()
-  try:
-    eng.rccl_init(0, 1, Engine.rccl_unique_id())
-    eng.trace_stats(0, 64)
-    eng.trace_ess(0, 64)
-    tr0, mom0, st0 = eng.trace(0, 64), eng.moments(), eng.state()
-    g0 = eng.rccl_allgather_stats()
+  def reduce(eng):
     a = eng.trace_quantile(QS, 3, 61, weighted=True)
     b = eng.trace_quantile(QS, 3, 61, weighted=True)
     assert a.tobytes() == b.tobytes()
     u = eng.trace_quantile(QS, 3, 61, weighted=False)
     assert u.tobytes() == eng.trace_quantile(QS, 3, 61, weighted=False).tobytes()
-    tr1, mom1, st1 = eng.trace(0, 64), eng.moments(), eng.state()
-    g1 = eng.rccl_allgather_stats()
-    for k in ('v_x', 'v_p', 'u'):
-      assert np.array_equal(tr0[k], tr1[k]), k
-    for k in ('sum', 'sumsq', 'n_acc'):
-      assert np.array_equal(mom0[k], mom1[k]), k
-      assert np.array_equal(g0[k], g1[k]), k
-    assert mom0['n_steps'] == mom1['n_steps']
-    assert np.isfinite(g0['ess']).all() and np.array_equal(g0['ess'], g1['ess'])
-    assert np.array_equal(st0[0], st1[0]) and np.array_equal(st0[1], st1[1])
-    # the run continues as it does without the call
-    eng.run(32, steps_per_launch=64)
-    ref.run(32, steps_per_launch=64)
-    ta, tb = eng.trace(), ref.trace()
-    for k in ('v_x', 'v_p', 'u'):
-      assert np.array_equal(ta[k], tb[k]), k
-    sa, sb = eng.state(), ref.state()
-    assert np.array_equal(sa[0], sb[0]) and np.array_equal(sa[1], sb[1])
-  finally:
-    eng.close()
-    ref.close()
+
+  check_no_side_effects(reduce, 515)
 
 
 # ---- with the resident server (the pattern of test_gpu_server.py) ----------

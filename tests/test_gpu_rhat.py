@@ -35,6 +35,7 @@ from oracle.workloads import golden_init
 from probayes_amd import diag
 from probayes_amd._lib import PbhError
 from rhat_reference import device_bound, ref_moments, ref_nested, ref_split, rel_dist
+from trace_helpers import check_no_side_effects, run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -46,22 +47,12 @@ WINDOWS = [(40, 120), (40, 119), (0, 4)]
 GROUPS = [1, 4, 12, 167, N_BIG // 2]
 
 
-def _run(spec, init, t, seed=3):
-  from probayes_amd import Engine
-  eng = Engine(spec)
-  eng.init_chains(init)
-  eng.set_rng('philox', seed=seed)
-  eng.alloc_trace(t, 1)
-  eng.run(t, steps_per_launch=64)
-  return eng
-
-
 @functools.lru_cache(maxsize=None)
 def _big(name):
   """One run per model: the host copy of the trace and every device result,
   each asked for twice."""
   spec = oracle.golden_spec(name)
-  eng = _run(spec, golden_init(name, N_BIG), T_BIG)
+  eng = run(spec, golden_init(name, N_BIG), T_BIG)
   try:
     x = eng.trace()['v_x']
     dev, again = {}, {}
@@ -132,7 +123,7 @@ def test_two_calls_give_the_same_bits(name):
 
 def test_few_chains_and_optional_outputs():
   spec = oracle.golden_spec('gmm2')
-  eng = _run(spec, golden_init('gmm2', 6), 40)
+  eng = run(spec, golden_init('gmm2', 6), 40)
   try:
     x = eng.trace()['v_x']
     got = eng.trace_rhat(3, 37, 3, stats=True)
@@ -147,7 +138,7 @@ def test_few_chains_and_optional_outputs():
     assert only['split'].tobytes() == got['split'].tobytes()
   finally:
     eng.close()
-  eng = _run(spec, golden_init('gmm2', 1), 40)
+  eng = run(spec, golden_init('gmm2', 1), 40)
   try:
     x = eng.trace()['v_x']
     got = eng.trace_rhat(0, 40)
@@ -166,7 +157,7 @@ def test_many_chains():
   workgroup, also with a second batch; 2 200 chains stays within its first."""
   n, t = 33000, 8
   spec = oracle.golden_spec('gmm2')
-  eng = _run(spec, golden_init('gmm2', n), t)
+  eng = run(spec, golden_init('gmm2', n), t)
   try:
     x = eng.trace()['v_x']
     dev = {g: eng.trace_rhat(0, t, g) for g in (1, 2200, n // 2)}
@@ -186,7 +177,7 @@ def test_constant_chains():
   starts = np.array([[-1., 0.5], [0.25, 2.], [3., -1.]])
   for same in (True, False):
     x0 = np.repeat(starts[:1], 6, axis=0) if same else np.repeat(starts, 2, axis=0)
-    eng = _run(spec, x0, 12)
+    eng = run(spec, x0, 12)
     try:
       x = eng.trace()['v_x']
       assert (x == x0[:, None, :]).all()   # the chains did not move
@@ -203,43 +194,11 @@ def test_constant_chains():
 
 
 def test_no_side_effects():
-  from probayes_amd import Engine
-
-  def start():
-    eng = Engine(oracle.golden_spec('gmm2'))
-    eng.init_chains(golden_init('gmm2', 516))
-    eng.set_rng('philox', seed=9)
-    eng.alloc_trace(96, 1)
-    eng.run(64, steps_per_launch=64)
-    return eng
-
-  eng, ref = start(), start()
-  try:
-    st0 = eng.trace_stats(0, 64)
-    ess0 = eng.trace_ess(0, 64).copy()
-    tr0, mom0, x0 = eng.trace(0, 64), eng.moments(), eng.state()
+  def reduce(eng):
     eng.trace_rhat(3, 61, 4, stats=True)
     eng.trace_rhat(3, 60, 258)
-    tr1, mom1, x1 = eng.trace(0, 64), eng.moments(), eng.state()
-    for k in ('v_x', 'v_p', 'u'):
-      assert np.array_equal(tr0[k], tr1[k]), k
-    for k in ('sum', 'sumsq', 'n_acc'):
-      assert np.array_equal(mom0[k], mom1[k]), k
-    assert mom0['n_steps'] == mom1['n_steps']
-    assert np.array_equal(x0[0], x1[0]) and np.array_equal(x0[1], x1[1])
-    st1 = eng.trace_stats(0, 64)
-    for k in ('sum', 'sumsq', 'n_acc'):
-      assert np.array_equal(st0[k], st1[k]), k
-    assert np.array_equal(ess0, eng.trace_ess(0, 64))
-    # the run continues as it does without the calls
-    eng.run(32, steps_per_launch=64)
-    ref.run(32, steps_per_launch=64)
-    ta, tb = eng.trace(), ref.trace()
-    for k in ('v_x', 'v_p', 'u'):
-      assert np.array_equal(ta[k], tb[k]), k
-  finally:
-    eng.close()
-    ref.close()
+
+  check_no_side_effects(reduce, 516)
 
 
 def test_refusals_leave_the_engine_working():
