@@ -31,9 +31,9 @@ extern "C" {
 /* Additions that leave every version-7 call and struct prefix as it was bump
  * the revision: 1 = pbh_model.expr_data / expr_n_obs / expr_n_cols (a caller
  * passes the whole struct, zero-initialised), pbh_eval_expr_data;
- * 2 = pbh_trace_quantile.  pbh_trace_rhat and pbh_trace_quantile_pooled were
- * added within revision 2 without a bump: a caller finds them by looking the
- * symbol up.                                                                */
+ * 2 = pbh_trace_quantile.  pbh_trace_rhat, pbh_trace_quantile_pooled and
+ * pbh_trace_rhat_rank were added within revision 2 without a bump: a caller
+ * finds them by looking the symbol up.                                      */
 #define PBH_ABI_REVISION 2
 #define PBH_MAX_DIM 32
 
@@ -528,6 +528,38 @@ int pbh_trace_rhat(pbh_engine *eng, int64_t first, int64_t count, int32_t group,
 int pbh_trace_quantile_pooled(pbh_engine *eng, int64_t first, int64_t count,
                               int32_t nq, const double *q, double *out,
                               double *order_stats);
+
+/* Rank-normalised and folded split-R-hat (Vehtari et al. 2021) over trace
+ * records [first, first + count) on the device, per dim (added within
+ * revision 2 as pbh_trace_rhat was: PBH_ABI_REVISION did not change for it,
+ * look the symbol up).  probayes_amd/diag.py average_ranks / normal_scores /
+ * rank_rhat are the definition.  Per dim, over the M = N count values pooled
+ * over chains and records: the 1-based rank of each value, ties taking the
+ * mean of their ranks, -0.0 and +0.0 one value; the normal score z = Phi^-1((r
+ * - 3/8) / (M + 1/4)) by Wichura's AS241 (PPND16) in fp64; and split-R-hat of
+ * the scores as pbh_trace_rhat forms it of the values.
+ * bulk [d]: that, of the ranks of the values.  folded [d]: of the ranks of
+ * |x - med|, med the dim's pooled median (pbh_trace_quantile_pooled at q =
+ * 0.5, bit for bit).  The rank-normalised R-hat a caller reads is the larger
+ * of the two.
+ * ranks, folded_ranks [count][d][N]: the ranks themselves.
+ * Each of the four may be NULL; a variant is computed only if one of its two
+ * outputs is asked for, and with all four NULL the call returns PBH_ERR_ARG
+ * (whatever else it was given).  A dim that holds a NaN -- after folding also
+ * a NaN median or an inf - inf -- gives NaN for every rank and for both
+ * statistics; there are no other special cases (constant chains give W = 0
+ * and so inf or NaN, as pbh_trace_rhat does).
+ * The ranks come from a least-significant-digit radix sort of (key, element
+ * index) pairs over the monotone 64-bit image of the doubles, one dim and one
+ * variant at a time, in the engine's reduction scratch (about 40 bytes per
+ * element of a dim); every pass is stable and no atomic decides a position, so
+ * the ranks equal sorting on the host and two calls give the same bits.
+ * count >= 4; N count >= 2^32 is PBH_ERR_UNSUPPORTED (the element index is 32
+ * bits).  Changes nothing in the engine: not the moments, the ESS, the trace,
+ * the chains or the generators.                                             */
+int pbh_trace_rhat_rank(pbh_engine *eng, int64_t first, int64_t count,
+                        double *bulk, double *folded, double *ranks,
+                        double *folded_ranks);
 
 /* ---- multi-GPU: one RCCL all-gather over xGMI --------- */
 int pbh_rccl_unique_id(uint8_t id[128]);

@@ -279,6 +279,18 @@ hipError_t launch_select_init(uint64_t *sc, int32_t d, int32_t nt, const uint64_
 hipError_t launch_select_pass(const double *tx, int64_t n, int32_t d, int64_t first,
                               int64_t count, uint64_t *sc, int32_t nt, int32_t pass,
                               hipStream_t s);
+// The pooled ranks of dim k over trace records [first, first + count) and
+// their normal scores (pbh_rank.hip): a radix sort of (key_image, element
+// index) pairs, M = n count < 2^32 elements, element e = record n + chain.
+// med: null for the ranks of the values, else the device array [d] of pooled
+// medians, and the ranks are those of |x - med[k]|.  scratch / l: the reduction
+// scratch as rank_layout (pbh_trace_host.h) lays it out.  Leaves the scores z
+// [count][n] at scratch + l.z and, with want_ranks, the 1-based average ranks
+// at scratch + l.r (a dim that holds a NaN: all NaN).  No host round trip.
+struct RankLayout;
+hipError_t launch_rank_dim(const double *tx, int64_t n, int32_t d, int32_t k, int64_t first,
+                           int64_t count, const double *med, unsigned char *scratch,
+                           const RankLayout &l, bool want_ranks, hipStream_t s);
 // fft: 2 = the 2 048-point FFT form for count <= 1 536 records with the
 // 4 096-point form for the pairs it cannot decide (list: (d n + 1) / 2 + 1
 // int32 of device scratch), 1 = the 4 096-point form for count <= 2 048

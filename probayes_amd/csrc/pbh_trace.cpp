@@ -243,6 +243,91 @@ int pbh_trace_quantile_pooled(pbh_engine *e, int64_t first, int64_t count, int32
   return PBH_OK;
 }
 
+int pbh_trace_rhat_rank(pbh_engine *e, int64_t first, int64_t count, double *bulk,
+                        double *folded, double *ranks, double *folded_ranks) {
+  if (!bulk && !folded && !ranks && !folded_ranks)
+    return fail(PBH_ERR_ARG, "pbh_trace_rhat_rank: no output asked for (bulk, folded, ranks "
+                "and folded_ranks are all NULL)");
+  if (const int rc = trace_enter(e, {}, true, first, count, 0)) return rc;
+  if (count < 4)
+    return fail(PBH_ERR_ARG, "count = %lld: split R-hat needs at least 4 records "
+                "(two in each half)", (long long)count);
+  const int64_t n = e->n, d = e->d;
+  const bool want[2] = {bulk || ranks, folded || folded_ranks};
+  const bool want_ranks = ranks || folded_ranks;
+  // the folded variant's fold point: the pooled median, selected for all dims
+  const double half = 0.5;
+  pbh::PooledPlan plan;
+  int32_t nt = 0;
+  int64_t sel_words = 0;
+  if (want[1]) {
+    plan = pbh::pooled_plan(n * count, 1, &half);
+    nt = (int32_t)plan.ranks.size();
+    sel_words = pbh::select_scratch_words((int32_t)d, nt);
+  }
+  pbh::RankLayout l;
+  if (!pbh::rank_layout(n, count, (int32_t)d, sel_words, want_ranks, &l))
+    return fail(PBH_ERR_UNSUPPORTED, "%lld chains of %lld records: the pooled sort indexes "
+                "fewer than 2^32 elements per dim", (long long)n, (long long)count);
+  HIP_TRY(hipSetDevice(e->device));
+  if (const int rc = scratch(e, (size_t)l.bytes)) return rc;
+  unsigned char *sc = e->scratch;
+  double *med = reinterpret_cast<double *>(sc + l.med);
+  double *res = reinterpret_cast<double *>(sc + l.res);
+  double *stats = reinterpret_cast<double *>(sc + l.stats);
+  const double *z = reinterpret_cast<const double *>(sc + l.z);
+  const double *r = reinterpret_cast<const double *>(sc + l.r);
+  hipError_t err = hipSuccess;
+  double host_med[PBH_MAX_DIM];   // (alive until the stream has been synchronised)
+  if (want[1]) {
+    uint64_t *sel = reinterpret_cast<uint64_t *>(sc + l.select);
+    std::vector<uint64_t> init((size_t)(4 * d * pbh::kSelectMaxTargets + d));
+    err = pbh::launch_select_init(sel, (int32_t)d, nt, plan.ranks.data(), init.data(), e->stream);
+    for (int32_t pass = 0; err == hipSuccess && pass < pbh::select_passes(); ++pass)
+      err = pbh::launch_select_pass(e->tx, n, (int32_t)d, first, count, sel, nt, pass, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    std::vector<double> order((size_t)(d * nt));   // [d][nt]
+    if (err == hipSuccess)
+      err = hipMemcpy(order.data(), sel + pbh::select_stats_offset((int32_t)d, nt),
+                      order.size() * sizeof(double), hipMemcpyDeviceToHost);
+    if (err == hipSuccess) {
+      pbh::pooled_interpolate(plan, d, order.data(), host_med, nullptr);
+      err = hipMemcpyAsync(med, host_med, d * sizeof(double), hipMemcpyHostToDevice, e->stream);
+    }
+  }
+  for (int v = 0; v < 2; ++v) {
+    if (!want[v]) continue;
+    double *out_ranks = v ? folded_ranks : ranks;
+    const bool reduce = v ? folded != nullptr : bulk != nullptr;
+    for (int64_t k = 0; err == hipSuccess && k < d; ++k) {
+      err = pbh::launch_rank_dim(e->tx, n, (int32_t)d, (int32_t)k, first, count,
+                                 v ? med : nullptr, sc, l, out_ranks != nullptr, e->stream);
+      if (err == hipSuccess && reduce)
+        err = pbh::launch_rhat_chain(z, n, 1, 0, count, stats, e->stream);
+      if (err == hipSuccess && reduce)
+        err = pbh::launch_rhat_cross(stats, n, 1, count, 0, nullptr, res + v * d + k, nullptr,
+                                     e->stream);
+      if (err == hipSuccess && out_ranks) {
+        // the dim's [count][n] into the host's [count][d][n]
+        err = hipStreamSynchronize(e->stream);
+        if (err == hipSuccess)
+          err = hipMemcpy2D(out_ranks + k * n, (size_t)(d * n) * sizeof(double), r,
+                            (size_t)n * sizeof(double), (size_t)n * sizeof(double),
+                            (size_t)count, hipMemcpyDeviceToHost);
+      }
+    }
+  }
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  double host[2 * PBH_MAX_DIM];
+  if (err == hipSuccess && (bulk || folded))
+    err = hipMemcpy(host, res, 2 * d * sizeof(double), hipMemcpyDeviceToHost);
+  if (err != hipSuccess)
+    return fail(PBH_ERR_HIP, "pbh_trace_rhat_rank: %s", hipGetErrorString(err));
+  if (bulk) std::memcpy(bulk, host, d * sizeof(double));
+  if (folded) std::memcpy(folded, host + d, d * sizeof(double));
+  return PBH_OK;
+}
+
 int pbh_trace_ess(pbh_engine *e, int64_t first, int64_t count, double *ess) {
   if (const int rc = trace_enter(e, {}, false, first, count, 2, [] { return PBH_OK; }, kRangeEss))
     return rc;

@@ -78,4 +78,38 @@ void pooled_interpolate(const PooledPlan &p, int64_t d, const double *stats, dou
   }
 }
 
+bool rank_layout(int64_t n, int64_t count, int32_t d, int64_t select_words, bool want_ranks,
+                 RankLayout *out) {
+  int64_t M;
+  if (n < 1 || count < 1 || d < 1 || select_words < 0) return false;
+  if (__builtin_mul_overflow(n, count, &M) || M >= ((int64_t)1 << 32)) return false;
+  RankLayout l;
+  l.M = M;
+  l.tiles = (M + kRankTile - 1) / kRankTile;
+  l.chunk_tiles = (l.tiles + kRankMaxChunks - 1) / kRankMaxChunks;
+  l.chunks = (l.tiles + l.chunk_tiles - 1) / l.chunk_tiles;
+  int64_t at = 0;
+  const auto take = [&at](int64_t bytes) {
+    const int64_t here = at;
+    at += (bytes + 255) / 256 * 256;
+    return here;
+  };
+  l.select = take(select_words * 8);
+  l.med = take((int64_t)d * 8);
+  l.res = take(2 * (int64_t)d * 8);
+  l.state = take(8 * 4);
+  l.chunk = take(l.chunks * kRankBins * 4);
+  l.hist = take(l.tiles * kRankBins * 4);
+  l.stats = take(6 * n * 8);
+  l.key[0] = take(M * 8);
+  l.key[1] = take(M * 8);
+  l.idx[0] = take(M * 4);
+  l.idx[1] = take(M * 4);
+  l.z = take(M * 8);
+  l.r = want_ranks ? take(M * 8) : at;
+  l.bytes = at;
+  *out = l;
+  return true;
+}
+
 }  // namespace pbh

@@ -1,7 +1,8 @@
 // pbh_trace_host.h -- the host arithmetic of the trace reductions: the window
 // check every trace entry point makes, the checks of a quantile list, and the
-// host steps of the pooled quantile around the device's radix select.  No HIP:
-// a host compiler alone builds it (tests/trace_host_main.cpp).  Built with
+// host steps of the pooled quantile around the device's radix select, and the
+// geometry and scratch layout of the pooled sort (pbh_rank.hip).  No HIP: a host
+// compiler alone builds it (tests/trace_host_main.cpp, rank_host_main.cpp).  Built with
 // -ffp-contract=off: the interpolation must round as NumPy's does.
 #pragma once
 #include <stdint.h>
@@ -37,5 +38,29 @@ PooledPlan pooled_plan(int64_t M, int32_t nq, const double *q);
 // between.  A dim whose largest element is a NaN gives NaN for every q.
 void pooled_interpolate(const PooledPlan &p, int64_t d, const double *stats, double *out,
                         double *order_stats);
+
+// The geometry and the scratch of the pooled sort behind the rank-normalised
+// R-hat (pbh_rank.hip), which runs one dim and one variant at a time over M =
+// n count elements.  A tile is what one workgroup sorts by a digit; the
+// [tile][digit] table of a pass is scanned in `chunks` (at most
+// kRankMaxChunks) runs of chunk_tiles consecutive tiles.  The offsets are in
+// bytes from the start of the reduction scratch, each a multiple of 256, the
+// regions disjoint and in this order: the select's own scratch (the median),
+// med [d], res [2][d], the eight passes' skip flags, chunk [chunks][256] and
+// hist [tiles][256] (uint32), stats [6][n], the two key buffers (uint64 [M]),
+// the two index buffers (uint32 [M]), z [M] and, with want_ranks, r [M]
+// (doubles).
+constexpr int64_t kRankTile = 2048;
+constexpr int64_t kRankBins = 256;
+constexpr int64_t kRankMaxChunks = 256;
+struct RankLayout {
+  int64_t M, tiles, chunk_tiles, chunks;
+  int64_t select, med, res, state, chunk, hist, stats, key[2], idx[2], z, r, bytes;
+};
+// False when M = n count does not fit the 32-bit index the sort carries (M >=
+// 2^32, or the product leaves int64) or an argument is out of range (n, count
+// < 1, d < 1, select_words < 0); `out` is then untouched.
+bool rank_layout(int64_t n, int64_t count, int32_t d, int64_t select_words, bool want_ranks,
+                 RankLayout *out);
 
 }  // namespace pbh

@@ -15,6 +15,11 @@ NaN record propagates.
 
 pooled_quantile is the definition of the posterior quantiles pooled over every
 chain and record (pbh_trace_quantile_pooled, Engine.trace_quantile_pooled).
+
+average_ranks, normal_scores and rank_rhat are the definition of the
+rank-normalised and the folded split-R-hat (Vehtari et al. 2021;
+pbh_trace_rhat_rank, Engine.trace_rhat_rank): the ranks of every draw of a dim
+pooled over chains and records, their normal scores, and split_rhat of those.
 """
 import numpy as np
 
@@ -160,3 +165,137 @@ def pooled_quantile(x, q, first=0, count=None):
     if np.isnan(s[-1]):
       out[:, k] = np.nan
   return out
+
+
+def _window(what, x, first, count):
+  x = np.asarray(x, float)
+  if x.ndim != 3:
+    raise ValueError('{}: a trace [N, T, d], got shape {}'.format(what, x.shape))
+  first = int(first)
+  count = x.shape[1] - first if count is None else int(count)
+  if first < 0 or count < 0 or first + count > x.shape[1]:
+    raise ValueError('{}: records [{}, {}) outside [0, {})'.format(
+        what, first, first + count, x.shape[1]))
+  return x, first, count
+
+
+def average_ranks(x, first=0, count=None, fold=False):
+  """[N, count, d]: per dim, the 1-based rank of every value of a host trace x
+  [N, T, d] over records [first, first + count) among the M = N count values of
+  the dim pooled over chains and records.  Ties take the mean of their ranks
+  (a multiple of 1/2, exact in fp64); -0.0 and +0.0 are one value.  fold=True
+  ranks abs(x - med_k) instead, med_k = pooled_quantile(x, [.5], first, count)
+  [0, k].  A dim that holds a NaN -- after folding also a NaN median or an inf
+  - inf -- gives NaN for every rank of the dim."""
+  x, first, count = _window('average_ranks', x, first, count)
+  if count < 1 or x.shape[0] < 1:
+    raise ValueError('average_ranks: count = {}: at least 1 record of at least 1 '
+                     'chain'.format(count))
+  w = x[:, first:first + count, :]
+  if fold:
+    med = pooled_quantile(x, [.5], first, count)[0]
+    with np.errstate(invalid='ignore'):
+      w = np.abs(w - med)
+  n, _, d = w.shape
+  m = n * count
+  out = np.empty((n, count, d))
+  for k in range(d):   # a dim at a time: one contiguous copy to sort
+    v = w[:, :, k].ravel()
+    if np.isnan(v).any():
+      out[:, :, k] = np.nan
+      continue
+    order = np.argsort(v, kind='stable')
+    s = v[order]
+    head = np.ones(m, bool)
+    head[1:] = s[1:] != s[:-1]   # (-0.0 == +0.0)
+    starts = np.flatnonzero(head)
+    ends = np.append(starts[1:], m)
+    run = np.cumsum(head) - 1
+    r = np.empty(m)
+    r[order] = ((starts + ends + 1) * 0.5)[run]
+    out[:, :, k] = r.reshape(n, count)
+  return out
+
+
+# Wichura's AS241, PPND16: the coefficients of the three rational
+# approximations, highest power first, as CPython's statistics module lists
+# them.
+_A = (2.5090809287301226727e+3, 3.3430575583588128105e+4, 6.7265770927008700853e+4,
+      4.5921953931549871457e+4, 1.3731693765509461125e+4, 1.9715909503065514427e+3,
+      1.3314166789178437745e+2, 3.3871328727963666080e+0)
+_B = (5.2264952788528545610e+3, 2.8729085735721942674e+4, 3.9307895800092710610e+4,
+      2.1213794301586595867e+4, 5.3941960214247511077e+3, 6.8718700749205790830e+2,
+      4.2313330701600911252e+1, 1.0)
+_C = (7.74545014278341407640e-4, 2.27238449892691845833e-2, 2.41780725177450611770e-1,
+      1.27045825245236838258e+0, 3.64784832476320460504e+0, 5.76949722146069140550e+0,
+      4.63033784615654529590e+0, 1.42343711074968357734e+0)
+_D = (1.05075007164441684324e-9, 5.47593808499534494600e-4, 1.51986665636164571966e-2,
+      1.48103976427480074590e-1, 6.89767334985100004550e-1, 1.67638483018380384940e+0,
+      2.05319162663775882187e+0, 1.0)
+_E = (2.01033439929228813265e-7, 2.71155556874348757815e-5, 1.24266094738807843860e-3,
+      2.65321895265761230930e-2, 2.96560571828504891230e-1, 1.78482653991729133580e+0,
+      5.46378491116411436990e+0, 6.65790464350110377720e+0)
+_F = (2.04426310338993978564e-15, 1.42151175831644588870e-7, 1.84631831751005468180e-5,
+      7.86869131145613259100e-4, 1.48753612908506148525e-2, 1.36929880922735805310e-1,
+      5.99832206555887937690e-1, 1.0)
+
+
+def _horner(c, r):
+  acc = c[0] * r + c[1]
+  for ci in c[2:]:
+    acc = acc * r + ci
+  return acc
+
+
+def _ndtri(p):
+  """The standard normal quantile of p in (0, 1), elementwise: AS241 PPND16 in
+  fp64 in exactly the operation order of CPython's statistics.NormalDist.inv_cdf
+  (mu 0, sigma 1).  Three branches: |p - 1/2| <= 0.425 (no libm call), r =
+  sqrt(-log(min(p, 1 - p))) <= 5, and r > 5.  A NaN gives NaN."""
+  p = np.asarray(p, float)
+  q = p - 0.5
+  out = np.full(p.shape, np.nan)
+  with np.errstate(all='ignore'):
+    mid = np.abs(q) <= 0.425
+    r = 0.180625 - q[mid] * q[mid]
+    out[mid] = _horner(_A, r) * q[mid] / _horner(_B, r)
+    tail = ~mid & ~np.isnan(q)
+    qt = q[tail]
+    r = np.sqrt(-np.log(np.where(qt <= 0., p[tail], 1. - p[tail])))
+    near = r <= 5.
+    x = np.empty(r.shape)
+    rn = r[near] - 1.6
+    x[near] = _horner(_C, rn) / _horner(_D, rn)
+    rf = r[~near] - 5.
+    x[~near] = _horner(_E, rf) / _horner(_F, rf)
+    out[tail] = np.where(qt < 0., -x, x)
+  return out
+
+
+def normal_scores(r, M):
+  """ndtri((r - 0.375) / (M + 0.25)) of the 1-based average ranks r among M
+  values, elementwise (Blom's offsets, as Vehtari et al. 2021 take them);
+  ndtri is AS241 as _ndtri writes it out.  A NaN rank gives a NaN score."""
+  r = np.asarray(r, float)
+  return _ndtri((r - 0.375) / (float(M) + 0.25))
+
+
+def rank_rhat(x, first=0, count=None):
+  """{'bulk': [d], 'folded': [d], 'rhat': [d]}: the rank-normalised split-R-hat
+  of a host trace x [N, T, d] over records [first, first + count).  bulk is
+  split_rhat(chain_moments(z), count // 2) of the scores z = normal_scores(
+  average_ranks(x, first, count), N count); folded the same of the folded
+  ranks; rhat = np.maximum of the two, so a NaN propagates.  count >= 4.  No
+  other special cases: constant chains give W = 0 and so inf or NaN, as
+  split_rhat does."""
+  x, first, count = _window('rank_rhat', x, first, count)
+  if count < 4:
+    raise ValueError('rank_rhat: count = {}: split R-hat needs at least 4 records '
+                     '(two in each half)'.format(count))
+  m = x.shape[0] * count
+  res = {}
+  for key, fold in (('bulk', False), ('folded', True)):
+    z = normal_scores(average_ranks(x, first, count, fold), m)
+    res[key] = split_rhat(chain_moments(z), count // 2)
+  res['rhat'] = np.maximum(res['bulk'], res['folded'])
+  return res

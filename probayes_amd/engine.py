@@ -702,6 +702,30 @@ class Engine:
               None if stats is None else _dp(stats))
     return (out, stats) if order_stats else out
 
+  def trace_rhat_rank(self, first=0, count=None, ranks=False):
+    """The rank-normalised split-R-hat (Vehtari et al. 2021) of trace records
+    [first, first + count), per dim, computed on the device (diag.rank_rhat is
+    the definition): {'bulk': [d], 'folded': [d], 'rhat': [d]}.  bulk is
+    split-R-hat of the normal scores of the ranks of every draw pooled over
+    chains and records; folded the same of the ranks of |x - pooled median|,
+    which sees chains that agree in location but not in scale; rhat is the
+    larger of the two, the number to read.  count >= 4; N count < 2^32.
+    ranks=True adds 'ranks' and 'folded_ranks': [N, count, d], the 1-based
+    average ranks themselves (diag.average_ranks, exactly)."""
+    first, count = self._window(first, count)
+    d, n = self.dim, self.n
+    bulk, folded = np.empty(d), np.empty(d)
+    rows = [np.empty((count, d, n)) for _ in range(2)] if ranks else [None, None]
+    _lib.call('pbh_trace_rhat_rank', self._h, _c.c_int64(int(first)),
+              _c.c_int64(int(count)), _dp(bulk), _dp(folded),
+              None if rows[0] is None else _dp(rows[0]),
+              None if rows[1] is None else _dp(rows[1]))
+    res = {'bulk': bulk, 'folded': folded, 'rhat': np.maximum(bulk, folded)}
+    if ranks:
+      res['ranks'] = rows[0].transpose(2, 0, 1).copy()
+      res['folded_ranks'] = rows[1].transpose(2, 0, 1).copy()
+    return res
+
   def rccl_allreduce_max(self, value):
     v = _c.c_double(float(value))
     _lib.call('pbh_rccl_allreduce_max', self._h, _c.byref(v))

@@ -1416,6 +1416,21 @@ class Sampler:
             else {k: float(res[key][i]) for i, k in enumerate(self.names)}
             for key in ('split', 'nested')}
 
+  def trace_rhat_rank(self, first=0, count=None):
+    """The rank-normalised split-R-hat of every name, computed by the engine
+    from its device trace (Engine.trace_rhat_rank) without copying the trace
+    to the host: {'bulk': {name: value}, 'folded': {name: value}, 'rhat':
+    {name: value}} over records [first, first + count) (count >= 4) -- rhat,
+    the larger of the other two, is the number to read.  Covers the sampler's
+    first block while the engine still holds it, as trace_quantile does."""
+    first, count = self._device_window('trace_rhat_rank', first, count)
+    if count < 4:
+      raise ValueError('trace_rhat_rank: count = {}: split R-hat needs at least 4 '
+                       'records'.format(count))
+    res = self._eng.trace_rhat_rank(first, count)
+    return {key: {k: float(res[key][i]) for i, k in enumerate(self.names)}
+            for key in ('bulk', 'folded', 'rhat')}
+
   def trace_quantile_pooled(self, q, first=0, count=None):
     """The posterior quantiles q of every name, pooled over every chain and
     every record [first, first + count), computed by the engine from its
