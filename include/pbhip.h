@@ -31,9 +31,9 @@ extern "C" {
 /* Additions that leave every version-7 call and struct prefix as it was bump
  * the revision: 1 = pbh_model.expr_data / expr_n_obs / expr_n_cols (a caller
  * passes the whole struct, zero-initialised), pbh_eval_expr_data;
- * 2 = pbh_trace_quantile.  pbh_trace_rhat, pbh_trace_quantile_pooled and
- * pbh_trace_rhat_rank were added within revision 2 without a bump: a caller
- * finds them by looking the symbol up.                                      */
+ * 2 = pbh_trace_quantile.  pbh_trace_rhat, pbh_trace_quantile_pooled,
+ * pbh_trace_rhat_rank and pbh_trace_ess_rank were added within revision 2
+ * without a bump: a caller finds them by looking the symbol up.             */
 #define PBH_ABI_REVISION 2
 #define PBH_MAX_DIM 32
 
@@ -560,6 +560,45 @@ int pbh_trace_quantile_pooled(pbh_engine *eng, int64_t first, int64_t count,
 int pbh_trace_rhat_rank(pbh_engine *eng, int64_t first, int64_t count,
                         double *bulk, double *folded, double *ranks,
                         double *folded_ranks);
+
+/* Bulk- and tail-ESS across chains (Vehtari et al. 2021) over trace records
+ * [first, first + count) on the device, per dim (added within revision 2 as
+ * pbh_trace_rhat_rank was: PBH_ABI_REVISION did not change for it, look the
+ * symbol up).  probayes_amd/diag.py split_chain_acov / multi_chain_ess /
+ * rank_ess are the definition.  Per dim and variant, over the C = 2 N split
+ * chains of h = count / 2 records (first halves of the chains, then second
+ * halves; an odd count drops the middle record): the biased autocovariance of
+ * each split chain about its own mean, averaged over the split chains, A[t], t
+ * < h; and Stan's estimator from A and the split chains' means (Geyer's
+ * initial positive and monotone sequences over rho[t] = 1 - (A[0] h / (h - 1) -
+ * A[t]) / (A[0] + var_j m_j), tau floored at 1 / log10(C h), ESS = C h / tau).
+ * The variants are the series the estimator reads:
+ * bulk [d]: the normal scores of the pooled ranks (pbh_trace_rhat_rank's).
+ * tail_parts [2][d]: lower, then upper -- the indicators x <= q05 and x <= q95
+ * as 0. / 1., q the dim's pooled quantiles (pbh_trace_quantile_pooled at 0.05
+ * and 0.95, bit for bit).  tail [d]: the smaller of the two (a NaN propagates).
+ * basic [d]: the values themselves.
+ * mean_acov [4][d][h]: the A[t] of the variants, in the order bulk, tail_lower,
+ * tail_upper, basic; rows of a variant that was not computed are left
+ * untouched.
+ * Each of the five may be NULL; bulk asks for the bulk variant, tail or
+ * tail_parts for the two tail variants, basic for the basic one, mean_acov
+ * alone for all four, and with all five NULL the call returns PBH_ERR_ARG
+ * (whatever else it was given).  A dim that holds a NaN gives NaN everywhere;
+ * there are no other special cases (all chains constant and equal give NaN,
+ * constant chains that differ a finite value).
+ * The autocovariance is linear in the power spectrum: a kernel sums |FFT|^2
+ * of the centred, zero-padded split chains (4 096 points in fp64, two chains
+ * to a complex transform) in a fixed order without floating-point atomics, one
+ * inverse transform per dim and variant gives A, and the O(h) estimator runs
+ * on the host; two calls give the same bits.  count >= 4; count / 2 >
+ * PBH_ESS_RANK_MAX_HALF is PBH_ERR_UNSUPPORTED, and so is, for bulk, N count
+ * >= 2^32 (the sort's element index).  Changes nothing in the engine: not the
+ * moments, the per-chain ESS, the trace, the chains or the generators.       */
+#define PBH_ESS_RANK_MAX_HALF 2048
+int pbh_trace_ess_rank(pbh_engine *eng, int64_t first, int64_t count,
+                       double *bulk, double *tail, double *tail_parts,
+                       double *basic, double *mean_acov);
 
 /* ---- multi-GPU: one RCCL all-gather over xGMI --------- */
 int pbh_rccl_unique_id(uint8_t id[128]);

@@ -291,6 +291,23 @@ struct RankLayout;
 hipError_t launch_rank_dim(const double *tx, int64_t n, int32_t d, int32_t k, int64_t first,
                            int64_t count, const double *med, unsigned char *scratch,
                            const RankLayout &l, bool want_ranks, hipStream_t s);
+// The autocovariance of a series averaged over its 2 n split chains
+// (pbh_ess_rank.hip), for the bulk- and tail-ESS across chains.  base: record 0
+// of the window, chain 0 of the dim, `stride` doubles between records (the
+// trace at a dim: d n; the scores of a dim: n); count >= 4 records, count / 2
+// <= 2 048.  thr: null for the values, else the device address of the
+// threshold, and the series is x <= *thr as 0. / 1. (all NaN for a NaN
+// threshold).  l: ess_layout's geometry (pbh_trace_host.h).
+// launch_ess_spectrum leaves l.groups rows of 4 096 power sums at part and,
+// when both are given, the split chains' means at mean_first / mean_second
+// [n]; launch_ess_finish adds the rows in order and leaves A[t], t < count / 2,
+// at acov.  A fixed summation order, no floating-point atomics.
+struct EssLayout;
+hipError_t launch_ess_spectrum(const double *base, int64_t n, int64_t stride, int64_t count,
+                               const double *thr, const EssLayout &l, double *part,
+                               double *mean_first, double *mean_second, hipStream_t s);
+hipError_t launch_ess_finish(const double *part, int64_t n, const EssLayout &l, double *acov,
+                             hipStream_t s);
 // fft: 2 = the 2 048-point FFT form for count <= 1 536 records with the
 // 4 096-point form for the pairs it cannot decide (list: (d n + 1) / 2 + 1
 // int32 of device scratch), 1 = the 4 096-point form for count <= 2 048

@@ -328,6 +328,145 @@ int pbh_trace_rhat_rank(pbh_engine *e, int64_t first, int64_t count, double *bul
   return PBH_OK;
 }
 
+int pbh_trace_ess_rank(pbh_engine *e, int64_t first, int64_t count, double *bulk, double *tail,
+                       double *tail_parts, double *basic, double *mean_acov) {
+  if (!bulk && !tail && !tail_parts && !basic && !mean_acov)
+    return fail(PBH_ERR_ARG, "pbh_trace_ess_rank: no output asked for (bulk, tail, tail_parts, "
+                "basic and mean_acov are all NULL)");
+  if (const int rc = trace_enter(e, {}, true, first, count, 0)) return rc;
+  if (count < 4)
+    return fail(PBH_ERR_ARG, "count = %lld: the split chains need at least 4 records "
+                "(two in each half)", (long long)count);
+  if (count / 2 > PBH_ESS_RANK_MAX_HALF)
+    return fail(PBH_ERR_UNSUPPORTED, "count = %lld: at most %d records in each half of the "
+                "window (a 4 096-point transform)", (long long)count, PBH_ESS_RANK_MAX_HALF);
+  const int64_t n = e->n, d = e->d, h = count / 2, C = 2 * n;
+  // the variants: bulk, tail_lower, tail_upper, basic
+  const bool all = !bulk && !tail && !tail_parts && !basic;
+  const bool want_tail = all || tail || tail_parts;
+  const bool want[4] = {all || bulk, want_tail, want_tail, all || basic};
+  pbh::RankLayout rl{};
+  if (want[0] && !pbh::rank_layout(n, count, (int32_t)d, 0, false, &rl))
+    return fail(PBH_ERR_UNSUPPORTED, "%lld chains of %lld records: the pooled sort indexes "
+                "fewer than 2^32 elements per dim", (long long)n, (long long)count);
+  // the tail's thresholds: the pooled 5 % and 95 % quantiles, selected for all dims
+  const double q_tail[2] = {0.05, 0.95};
+  pbh::PooledPlan plan;
+  int32_t nt = 0;
+  int64_t sel_words = 0;
+  if (want_tail) {
+    plan = pbh::pooled_plan(n * count, 2, q_tail);
+    nt = (int32_t)plan.ranks.size();
+    sel_words = pbh::select_scratch_words((int32_t)d, nt);
+  }
+  pbh::EssLayout l;
+  if (!pbh::ess_layout(n, count, (int32_t)d, want[0] ? rl.bytes : 0, sel_words, &l))
+    return fail(PBH_ERR_ARG, "pbh_trace_ess_rank: no scratch layout for %lld chains of %lld "
+                "records", (long long)n, (long long)count);
+  HIP_TRY(hipSetDevice(e->device));
+  if (const int rc = scratch(e, (size_t)l.bytes)) return rc;
+  unsigned char *sc = e->scratch;
+  double *thr = reinterpret_cast<double *>(sc + l.thr);
+  double *part = reinterpret_cast<double *>(sc + l.part);
+  double *acov = reinterpret_cast<double *>(sc + l.acov);     // [4][d][h]
+  double *means = reinterpret_cast<double *>(sc + l.means);   // [4][2][d][n]
+  double *stats = reinterpret_cast<double *>(sc + l.stats);   // [6][d][n]
+  const size_t row = (size_t)n * sizeof(double);
+  const auto mean_at = [&](int v, int half, int64_t k) { return means + ((v * 2 + half) * d + k) * n; };
+  hipError_t err = hipSuccess;
+  double host_thr[2 * PBH_MAX_DIM];   // (alive until the stream has been synchronised)
+  if (want_tail) {
+    uint64_t *sel = reinterpret_cast<uint64_t *>(sc + l.select);
+    std::vector<uint64_t> init((size_t)(4 * d * pbh::kSelectMaxTargets + d));
+    err = pbh::launch_select_init(sel, (int32_t)d, nt, plan.ranks.data(), init.data(), e->stream);
+    for (int32_t pass = 0; err == hipSuccess && pass < pbh::select_passes(); ++pass)
+      err = pbh::launch_select_pass(e->tx, n, (int32_t)d, first, count, sel, nt, pass, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    std::vector<double> order((size_t)(d * nt));   // [d][nt]
+    if (err == hipSuccess)
+      err = hipMemcpy(order.data(), sel + pbh::select_stats_offset((int32_t)d, nt),
+                      order.size() * sizeof(double), hipMemcpyDeviceToHost);
+    if (err == hipSuccess) {
+      pbh::pooled_interpolate(plan, d, order.data(), host_thr, nullptr);   // [2][d]
+      err = hipMemcpyAsync(thr, host_thr, 2 * d * sizeof(double), hipMemcpyHostToDevice,
+                           e->stream);
+    }
+  }
+  if (want[0]) {
+    // per dim: the scores z [count][n] as a one-dim trace, their half means
+    // from rhat_chain's rows
+    const double *z = reinterpret_cast<const double *>(sc + rl.z);
+    double *zstats = reinterpret_cast<double *>(sc + rl.stats);   // [6][n]
+    for (int64_t k = 0; err == hipSuccess && k < d; ++k) {
+      err = pbh::launch_rank_dim(e->tx, n, (int32_t)d, (int32_t)k, first, count, nullptr, sc, rl,
+                                 false, e->stream);
+      if (err == hipSuccess) err = pbh::launch_rhat_chain(z, n, 1, 0, count, zstats, e->stream);
+      if (err == hipSuccess)
+        err = pbh::launch_ess_spectrum(z, n, n, count, nullptr, l, part, nullptr, nullptr,
+                                       e->stream);
+      if (err == hipSuccess) err = pbh::launch_ess_finish(part, n, l, acov + k * h, e->stream);
+      for (int half = 0; err == hipSuccess && half < 2; ++half)
+        err = hipMemcpyAsync(mean_at(0, half, k), zstats + 2 * half * n, row,
+                             hipMemcpyDeviceToDevice, e->stream);
+    }
+  }
+  if (err == hipSuccess && want[3]) {
+    err = pbh::launch_rhat_chain(e->tx, n, (int32_t)d, first, count, stats, e->stream);
+    for (int half = 0; err == hipSuccess && half < 2; ++half)
+      err = hipMemcpyAsync(mean_at(3, half, 0), stats + 2 * half * d * n, (size_t)d * row,
+                           hipMemcpyDeviceToDevice, e->stream);
+  }
+  for (int v = 1; v < 4; ++v) {
+    if (!want[v]) continue;
+    const bool ind = v < 3;
+    for (int64_t k = 0; err == hipSuccess && k < d; ++k) {
+      err = pbh::launch_ess_spectrum(e->tx + (first * d + k) * n, n, d * n, count,
+                                     ind ? thr + (v - 1) * d + k : nullptr, l, part,
+                                     ind ? mean_at(v, 0, k) : nullptr,
+                                     ind ? mean_at(v, 1, k) : nullptr, e->stream);
+      if (err == hipSuccess)
+        err = pbh::launch_ess_finish(part, n, l, acov + (v * d + k) * h, e->stream);
+    }
+  }
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  // the host stage: A and the means of the variants computed, then the estimator
+  std::vector<double> hA((size_t)(d * h)), hm((size_t)(2 * d * n)), m((size_t)C);
+  double ess[4][PBH_MAX_DIM];
+  for (int v = 0; err == hipSuccess && v < 4; ++v) {
+    if (!want[v]) continue;
+    err = hipMemcpy(hA.data(), acov + v * d * h, hA.size() * sizeof(double),
+                    hipMemcpyDeviceToHost);
+    if (err == hipSuccess)
+      err = hipMemcpy(hm.data(), mean_at(v, 0, 0), hm.size() * sizeof(double),
+                      hipMemcpyDeviceToHost);
+    if (err != hipSuccess) break;
+    for (int64_t k = 0; k < d; ++k) {
+      std::memcpy(m.data(), hm.data() + k * n, row);
+      std::memcpy(m.data() + n, hm.data() + (d + k) * n, row);
+      ess[v][k] = pbh::multi_chain_ess(m.data(), hA.data() + k * h, C, h);
+    }
+    if (mean_acov) std::memcpy(mean_acov + v * d * h, hA.data(), hA.size() * sizeof(double));
+  }
+  if (err != hipSuccess) {
+    // (host_thr's copy may still be queued: it must not outlive this frame)
+    (void)hipStreamSynchronize(e->stream);
+    return fail(PBH_ERR_HIP, "pbh_trace_ess_rank: %s", hipGetErrorString(err));
+  }
+  if (bulk) std::memcpy(bulk, ess[0], d * sizeof(double));
+  if (basic) std::memcpy(basic, ess[3], d * sizeof(double));
+  if (tail_parts) {
+    std::memcpy(tail_parts, ess[1], d * sizeof(double));
+    std::memcpy(tail_parts + d, ess[2], d * sizeof(double));
+  }
+  if (tail)
+    for (int64_t k = 0; k < d; ++k) {
+      // np.minimum: a NaN propagates
+      const double a = ess[1][k], b = ess[2][k];
+      tail[k] = a != a ? a : b != b ? b : b < a ? b : a;
+    }
+  return PBH_OK;
+}
+
 int pbh_trace_ess(pbh_engine *e, int64_t first, int64_t count, double *ess) {
   if (const int rc = trace_enter(e, {}, false, first, count, 2, [] { return PBH_OK; }, kRangeEss))
     return rc;

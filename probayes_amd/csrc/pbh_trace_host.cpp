@@ -112,4 +112,69 @@ bool rank_layout(int64_t n, int64_t count, int32_t d, int64_t select_words, bool
   return true;
 }
 
+bool ess_layout(int64_t n, int64_t count, int32_t d, int64_t base, int64_t select_words,
+                EssLayout *out) {
+  if (n < 1 || count < 4 || count / 2 > PBH_ESS_RANK_MAX_HALF || d < 1 || base < 0 ||
+      base % 256 != 0 || select_words < 0)
+    return false;
+  EssLayout l;
+  l.h = count / 2;
+  l.pairs = n / 2 + n % 2;
+  l.run = (l.pairs + kEssMaxGroups - 1) / kEssMaxGroups;
+  l.groups = (l.pairs + l.run - 1) / l.run;
+  int64_t at = base;
+  const auto take = [&at](int64_t bytes) {
+    const int64_t here = at;
+    at += (bytes + 255) / 256 * 256;
+    return here;
+  };
+  l.select = take(select_words * 8);
+  l.thr = take(2 * (int64_t)d * 8);
+  l.part = take(l.groups * kEssPoints * 8);
+  l.acov = take(4 * (int64_t)d * l.h * 8);
+  l.means = take(4 * 2 * (int64_t)d * n * 8);
+  l.stats = take(6 * (int64_t)d * n * 8);
+  l.bytes = at;
+  *out = l;
+  return true;
+}
+
+double multi_chain_ess(const double *m, const double *A, int64_t C, int64_t h,
+                       int64_t *k_star) {
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const double mean_var = A[0] * (double)h / ((double)h - 1.);
+  // (of m - m[0]: equal means have variance 0 exactly)
+  double sm = 0.;
+  for (int64_t j = 0; j < C; ++j) sm += m[j] - m[0];
+  const double mbar = sm / (double)C;
+  double sd = 0.;
+  for (int64_t j = 0; j < C; ++j) {
+    const double dev = (m[j] - m[0]) - mbar;
+    sd += dev * dev;
+  }
+  const double var_plus = A[0] + sd / ((double)C - 1.);
+  const auto rho = [&](int64_t t) { return t == 0 ? 1. : 1. - (mean_var - A[t]) / var_plus; };
+  const auto pair = [&](int64_t k) { return rho(2 * k) + rho(2 * k + 1); };
+  const int64_t K = h / 2;
+  int64_t ks = K;
+  for (int64_t k = 1; k < K; ++k)
+    if (!(pair(k) > 0.)) {
+      ks = k;
+      break;
+    }
+  // the running minimum as np.minimum forms it: a NaN stays
+  double run = pair(0), sum = run;
+  for (int64_t k = 1; k < ks; ++k) {
+    const double p = pair(k);
+    run = run != run ? run : p != p ? p : p < run ? p : run;
+    sum += run;
+  }
+  double tau = -1. + 2. * sum;
+  if (ks < K && rho(2 * ks) > 0.) tau = tau + rho(2 * ks);
+  const double floor_tau = 1. / std::log10((double)C * (double)h);
+  tau = tau != tau ? nan : floor_tau > tau ? floor_tau : tau;
+  if (k_star) *k_star = ks;
+  return (double)C * (double)h / tau;
+}
+
 }  // namespace pbh

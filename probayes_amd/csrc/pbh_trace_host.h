@@ -1,9 +1,11 @@
 // pbh_trace_host.h -- the host arithmetic of the trace reductions: the window
 // check every trace entry point makes, the checks of a quantile list, and the
 // host steps of the pooled quantile around the device's radix select, and the
-// geometry and scratch layout of the pooled sort (pbh_rank.hip).  No HIP: a host
-// compiler alone builds it (tests/trace_host_main.cpp, rank_host_main.cpp).  Built with
-// -ffp-contract=off: the interpolation must round as NumPy's does.
+// geometry and scratch layout of the pooled sort (pbh_rank.hip), and the layout
+// and the estimator of the ESS across chains (pbh_ess_rank.hip).  No HIP: a host
+// compiler alone builds it (tests/trace_host_main.cpp, rank_host_main.cpp,
+// ess_host_main.cpp).  Built with -ffp-contract=off: the interpolation and the
+// estimator must round as NumPy's do.
 #pragma once
 #include <stdint.h>
 
@@ -62,5 +64,35 @@ struct RankLayout {
 // < 1, d < 1, select_words < 0); `out` is then untouched.
 bool rank_layout(int64_t n, int64_t count, int32_t d, int64_t select_words, bool want_ranks,
                  RankLayout *out);
+
+// The bulk- and tail-ESS across chains (pbh_ess_rank.hip), one dim and one
+// variant (bulk, tail_lower, tail_upper, basic) at a time.  The ceil(n / 2)
+// chain pairs of a dim are cut into `groups` (at most kEssMaxGroups) runs of
+// `run` consecutive pairs, a workgroup and a partial row of kEssPoints power
+// sums each.  The scratch behind `base` bytes (RankLayout.bytes when the bulk
+// variant sorts, else 0), each offset a multiple of 256, the regions disjoint
+// and in this order: the select's own scratch (the tail's two quantiles), thr
+// [2][d], part [groups][kEssPoints], acov [4][d][h], means [4][2][d][n] (first
+// halves, second halves) and stats [6][d][n] (the values' rows of
+// launch_rhat_chain).
+constexpr int64_t kEssPoints = 4096;
+constexpr int64_t kEssMaxGroups = 512;
+struct EssLayout {
+  int64_t h, pairs, run, groups;
+  int64_t select, thr, part, acov, means, stats, bytes;
+};
+// False when an argument is out of range (n < 1, count < 4, count / 2 >
+// PBH_ESS_RANK_MAX_HALF, d < 1, base < 0 or no multiple of 256, select_words <
+// 0); `out` is then untouched.
+bool ess_layout(int64_t n, int64_t count, int32_t d, int64_t base, int64_t select_words,
+                EssLayout *out);
+
+// The effective sample size of C split chains of h records from their means m
+// [C] and mean autocovariance A [h]: diag.multi_chain_ess in exactly its
+// operation order (the variance of the means, rho, Geyer's pairs, the scan,
+// the running minimum, tau), so the two give the same bits.  C >= 2, h >= 2.
+// k_star (may be null): where the scan stopped.
+double multi_chain_ess(const double *m, const double *A, int64_t C, int64_t h,
+                       int64_t *k_star = nullptr);
 
 }  // namespace pbh

@@ -20,7 +20,14 @@ average_ranks, normal_scores and rank_rhat are the definition of the
 rank-normalised and the folded split-R-hat (Vehtari et al. 2021;
 pbh_trace_rhat_rank, Engine.trace_rhat_rank): the ranks of every draw of a dim
 pooled over chains and records, their normal scores, and split_rhat of those.
+
+split_chain_acov, multi_chain_ess and rank_ess are the definition of the bulk-
+and tail-ESS of the same paper (pbh_trace_ess_rank, Engine.trace_ess_rank):
+the autocovariance averaged over the split chains, and Stan's estimator of the
+effective sample size from it.
 """
+import math
+
 import numpy as np
 
 ROWS = ('mean_first', 'var_first', 'mean_second', 'var_second', 'mean', 'var')
@@ -298,4 +305,129 @@ def rank_rhat(x, first=0, count=None):
     z = normal_scores(average_ranks(x, first, count, fold), m)
     res[key] = split_rhat(chain_moments(z), count // 2)
   res['rhat'] = np.maximum(res['bulk'], res['folded'])
+  return res
+
+
+def _seq_sum(v):
+  """The sum of a 1-D array added in index order (np.sum adds pairwise): the
+  order pbh_trace_host.cpp's multi_chain_ess adds in."""
+  return np.cumsum(v)[-1] if v.size else 0.
+
+
+def split_chain_acov(y, first=0, count=None):
+  """(m [C], A [h]) of a series y [N, T] of one dim over records [first, first +
+  count), h = count // 2: the C = 2 N split chains are the first halves [first,
+  first + h) of chains 0 .. N - 1, then the second halves [first + count - h,
+  first + count) -- the order split_rhat concatenates in; an odd count leaves
+  the middle record out.  Per split chain j the mean m_j and the biased
+  autocovariance a_j[t] = (1 / h) sum_{i = 0}^{h - 1 - t} (y_i - m_j) (y_{i + t} -
+  m_j), t = 0 .. h - 1; A[t] = mean_j a_j[t].
+  In fp64: m is chain_moments' mean_first and mean_second.  The sums of
+  products are linear in the power spectrum, so the split chains, each centred
+  by its first record plus the mean of its differences from it (a constant
+  chain is centred to exact zeros), are zero-padded to a power of two >= 2 h
+  and transformed, the power spectra summed over j, and one inverse transform
+  gives h C A[t].  count >= 2.  A NaN record gives NaN for every A[t]."""
+  y = np.asarray(y, float)
+  if y.ndim != 2:
+    raise ValueError('split_chain_acov: a series [N, T], got shape {}'.format(y.shape))
+  x, first, count = _window('split_chain_acov', y[:, :, None], first, count)
+  if count < 2 or x.shape[0] < 1:
+    raise ValueError('split_chain_acov: count = {}: at least 2 records of at least 1 '
+                     'chain'.format(count))
+  h = count // 2
+  mom = chain_moments(x, first, count)
+  m = np.concatenate([mom[0, :, 0], mom[2, :, 0]])
+  w = y[:, first:first + count]
+  halves = np.concatenate([w[:, :h], w[:, count - h:]], axis=0)   # [C, h]
+  c_all = halves.shape[0]
+  size = 1
+  while size < 2 * h:
+    size *= 2
+  power = np.zeros(size // 2 + 1)
+  with np.errstate(all='ignore'):
+    for j0 in range(0, c_all, 4096):   # (a block of split chains at a time)
+      blk = halves[j0:j0 + 4096]
+      v = blk - blk[:, :1]
+      v = v - (v.sum(axis=1) / float(h))[:, None]
+      f = np.fft.rfft(v, size, axis=1)
+      power += (f.real * f.real + f.imag * f.imag).sum(axis=0)
+    acov = np.fft.irfft(power, size)[:h] / (float(h) * float(c_all))
+  return m, acov
+
+
+def multi_chain_ess(m, A, C, h):
+  """The effective sample size of C split chains of h records each from their
+  means m [C] and their mean autocovariance A [h] (split_chain_acov): Stan's
+  estimator (Vehtari et al. 2021 section 3.2; Geyer's initial positive and
+  monotone sequences), every sum added in index order:
+    mean_var = A[0] h / (h - 1);  var_plus = A[0] + var_j m_j (ddof 1: the mean
+    of m - m[0] first, then the squared deviations of m - m[0] from it, so
+    that equal means have variance 0 exactly);
+    rho[t] = 1 - (mean_var - A[t]) / var_plus, rho[0] = 1;
+    P_k = rho[2 k] + rho[2 k + 1], k = 0 .. K - 1, K = h // 2;
+    k* = the first k in 1 .. K - 1 for which P_k > 0 is false (a NaN stops the
+    scan), K if there is none;
+    P'_0 = P_0, P'_k = np.minimum(P'_{k - 1}, P_k) for k < k* (a NaN propagates);
+    tau = -1 + 2 sum_{k < k*} P'_k, plus rho[2 k*] if k* < K and rho[2 k*] > 0;
+    tau = np.maximum(tau, 1 / log10(C h));  ESS = C h / tau.
+  There are no other special cases: all chains constant and equal give NaN
+  (0 / 0), a NaN record gives NaN, constant chains that differ a finite value
+  (rho = 1 throughout).  C >= 2, h >= 2."""
+  m = np.asarray(m, float).ravel()
+  A = np.asarray(A, float).ravel()
+  C, h = int(C), int(h)
+  if C < 2 or h < 2 or m.size != C or A.size != h:
+    raise ValueError('multi_chain_ess: C = {} (>= 2) means and h = {} (>= 2) lags, got {} '
+                     'and {}'.format(C, h, m.size, A.size))
+  with np.errstate(all='ignore'):
+    mean_var = A[0] * float(h) / (h - 1.)
+    dev = m - m[0]
+    dev = dev - _seq_sum(dev) / float(C)
+    var_plus = A[0] + _seq_sum(dev * dev) / (C - 1.)
+    rho = 1. - (mean_var - A) / var_plus
+    rho[0] = 1.
+    K = h // 2
+    P = rho[0:2 * K:2] + rho[1:2 * K:2]
+    bad = np.flatnonzero(~(P[1:] > 0.))
+    ks = int(bad[0]) + 1 if bad.size else K
+    mono = np.minimum.accumulate(P[:ks])
+    tau = -1. + 2. * _seq_sum(mono)
+    if ks < K and rho[2 * ks] > 0.:
+      tau = tau + rho[2 * ks]
+    tau = np.maximum(tau, 1. / math.log10(float(C) * float(h)))
+    return float(C) * float(h) / tau
+
+
+def rank_ess(x, first=0, count=None):
+  """{'bulk': [d], 'tail': [d], 'tail_lower': [d], 'tail_upper': [d], 'basic':
+  [d]}: the effective sample sizes of a host trace x [N, T, d] over records
+  [first, first + count), across the 2 N split chains (Vehtari et al. 2021).
+  Each is multi_chain_ess(*split_chain_acov(s), 2 N, count // 2) of a series s
+  per dim: bulk of the scores normal_scores(average_ranks(x, first, count), N
+  count); tail_lower and tail_upper of the indicators x <= q05 and x <= q95 as
+  0. / 1. (not rank-normalised), q = pooled_quantile(x, [.05, .95], first,
+  count); tail = np.minimum of the two; basic of the values themselves.  count
+  >= 4.  A dim that holds a NaN gives NaN everywhere (its indicators are NaN)."""
+  x, first, count = _window('rank_ess', x, first, count)
+  if count < 4:
+    raise ValueError('rank_ess: count = {}: the split chains need at least 4 records '
+                     '(two in each half)'.format(count))
+  n, _, d = x.shape
+  if n < 1:
+    raise ValueError('rank_ess: a trace without chains')
+  h, c_all = count // 2, 2 * n
+  w = x[:, first:first + count, :]
+  z = normal_scores(average_ranks(x, first, count), n * count)
+  q = pooled_quantile(x, [.05, .95], first, count)
+  res = {key: np.empty(d) for key in ('bulk', 'tail_lower', 'tail_upper', 'basic')}
+  for k in range(d):
+    series = {'bulk': z[:, :, k], 'basic': w[:, :, k]}
+    for key, thr in (('tail_lower', q[0, k]), ('tail_upper', q[1, k])):
+      with np.errstate(invalid='ignore'):
+        series[key] = np.where(np.isnan(thr), np.nan, (w[:, :, k] <= thr).astype(float))
+    for key, s in series.items():
+      m, acov = split_chain_acov(s)
+      res[key][k] = multi_chain_ess(m, acov, c_all, h)
+  res['tail'] = np.minimum(res['tail_lower'], res['tail_upper'])
   return res

@@ -726,6 +726,36 @@ class Engine:
       res['folded_ranks'] = rows[1].transpose(2, 0, 1).copy()
     return res
 
+  def trace_ess_rank(self, first=0, count=None, basic=False, acov=False):
+    """The bulk- and tail-ESS across chains (Vehtari et al. 2021) of trace
+    records [first, first + count), per dim, computed on the device
+    (diag.rank_ess is the definition): {'bulk': [d], 'tail': [d], 'tail_lower':
+    [d], 'tail_upper': [d]}, the effective sample sizes to read beside the
+    rank-normalised R-hat.  Each is Stan's estimator over the 2 N split chains
+    from their means and their averaged autocovariance: bulk of the normal
+    scores of the pooled ranks, tail_lower / tail_upper of the indicators x <=
+    the pooled 5 % / 95 % quantile, tail the smaller of the two.  basic=True
+    adds 'basic', the same of the values themselves.  acov=True adds 'acov':
+    {variant: [d, h]}, the averaged autocovariances A[t], t < h = count // 2, of
+    every variant computed.  count >= 4, count // 2 <= 2 048; N count < 2^32."""
+    first, count = self._window(first, count)
+    d, h = self.dim, max(int(count) // 2, 0)
+    bulk, tail, parts = np.empty(d), np.empty(d), np.empty((2, d))
+    vals = np.empty(d) if basic else None
+    rows = np.empty((4, d, h)) if acov else None
+    _lib.call('pbh_trace_ess_rank', self._h, _c.c_int64(int(first)),
+              _c.c_int64(int(count)), _dp(bulk), _dp(tail), _dp(parts),
+              None if vals is None else _dp(vals), None if rows is None else _dp(rows))
+    res = {'bulk': bulk, 'tail': tail, 'tail_lower': parts[0].copy(),
+           'tail_upper': parts[1].copy()}
+    if basic:
+      res['basic'] = vals
+    if acov:
+      res['acov'] = {key: rows[v].copy()
+                     for v, key in enumerate(('bulk', 'tail_lower', 'tail_upper', 'basic'))
+                     if basic or key != 'basic'}
+    return res
+
   def rccl_allreduce_max(self, value):
     v = _c.c_double(float(value))
     _lib.call('pbh_rccl_allreduce_max', self._h, _c.byref(v))

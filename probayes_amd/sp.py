@@ -1431,6 +1431,22 @@ class Sampler:
     return {key: {k: float(res[key][i]) for i, k in enumerate(self.names)}
             for key in ('bulk', 'folded', 'rhat')}
 
+  def trace_ess_rank(self, first=0, count=None):
+    """The bulk- and tail-ESS across chains of every name, computed by the
+    engine from its device trace (Engine.trace_ess_rank) without copying the
+    trace to the host: {'bulk': {name: value}, 'tail': {name: value},
+    'tail_lower': ..., 'tail_upper': ...} over records [first, first + count)
+    (count >= 4, at most 2 048 records in each half) -- the effective sample
+    sizes to read beside trace_rhat_rank's rhat.  Covers the sampler's first
+    block while the engine still holds it, as trace_quantile does."""
+    first, count = self._device_window('trace_ess_rank', first, count)
+    if count < 4:
+      raise ValueError('trace_ess_rank: count = {}: the split chains need at least 4 '
+                       'records'.format(count))
+    res = self._eng.trace_ess_rank(first, count)
+    return {key: {k: float(res[key][i]) for i, k in enumerate(self.names)}
+            for key in ('bulk', 'tail', 'tail_lower', 'tail_upper')}
+
   def trace_quantile_pooled(self, q, first=0, count=None):
     """The posterior quantiles q of every name, pooled over every chain and
     every record [first, first + count), computed by the engine from its
