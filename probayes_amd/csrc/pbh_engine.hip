@@ -563,7 +563,7 @@ int pbh_destroy(pbh_engine *e) {
   put(e->gather_send); put(e->gather_recv); put(e->scalar);
   put(e->bm64); put(e->ess); put(e->lgtab); put(e->ess_list); put(e->ess_tot);
   put(e->scratch);
-  if (e->ess_host) (void)hipHostFree(e->ess_host);
+  if (e->stage) (void)hipHostFree(e->stage);
   if (e->srv_cmd) (void)hipHostFree(e->srv_cmd);
   if (e->srv_done) (void)hipHostFree(e->srv_done);
   dfree(e->srv_mail);

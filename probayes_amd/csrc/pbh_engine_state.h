@@ -72,8 +72,8 @@ struct pbh_engine {
   double *ess = nullptr;     // [d][n] per-chain ESS (pbh_trace_ess), NaN before
   int32_t *ess_list = nullptr;   // the 2 048-point ESS form's fallback list
   size_t ess_list_len = 0;
-  double *ess_host = nullptr;    // pinned staging of the ESS copy-out
-  size_t ess_host_len = 0;
+  double *stage = nullptr;       // pinned staging of doubles: the ESS copy-out, and
+  size_t stage_len = 0;          // the selected quantiles the rank reductions upload
   // The one scratch of the trace reductions (expectation, quantile, R-hat,
   // pooled quantile), grown on demand and kept between calls.  Each call
   // writes all it reads and has copied its result out when it returns, so

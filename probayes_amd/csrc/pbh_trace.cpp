@@ -62,14 +62,76 @@ int scratch(pbh_engine *e, size_t bytes) {
 }
 
 // the pinned staging buffer at n doubles or more
-int ess_host(pbh_engine *e, size_t n) {
-  if (e->ess_host_len >= n) return PBH_OK;
-  if (e->ess_host) (void)hipHostFree(e->ess_host);
-  e->ess_host = nullptr;
-  e->ess_host_len = 0;
-  HIP_TRY(hipHostMalloc(&e->ess_host, n * sizeof(double), hipHostMallocDefault));
-  e->ess_host_len = n;
+int stage(pbh_engine *e, size_t n) {
+  if (e->stage_len >= n) return PBH_OK;
+  if (e->stage) (void)hipHostFree(e->stage);
+  e->stage = nullptr;
+  e->stage_len = 0;
+  HIP_TRY(hipHostMalloc(&e->stage, n * sizeof(double), hipHostMallocDefault));
+  e->stage_len = n;
   return PBH_OK;
+}
+
+// the typed region of the reduction scratch that starts `byte_offset` in
+template <class T>
+T *at(unsigned char *scratch, int64_t byte_offset) {
+  return reinterpret_cast<T *>(scratch + byte_offset);
+}
+
+// what an entry point says of a HIP call that failed
+int hip_fail(const char *entry, hipError_t err) {
+  return fail(PBH_ERR_HIP, "%s: %s", entry, hipGetErrorString(err));
+}
+
+// A pooled radix select as far as it is decided before the scratch is sized:
+// where the quantiles lie among M values, the nt ranks the device selects, and
+// the select's scratch words for d dims (default: no select, no words).
+struct PooledSelect {
+  pbh::PooledPlan plan;
+  int32_t nt = 0;
+  int64_t words = 0;
+  PooledSelect() = default;
+  PooledSelect(int64_t M, int32_t d, int32_t nq, const double *q)
+      : plan(pbh::pooled_plan(M, nq, q)), nt((int32_t)plan.ranks.size()),
+        words(pbh::select_scratch_words(d, nt)) {}
+};
+
+// Runs the select over records [first, first + count) on the engine's stream in
+// the scratch words at `sel` and leaves the interpolated quantiles [nq][d] in
+// the host memory `out` (and, not null, order_stats [nq][2][d]).  The lifetime
+// rule of launch_select_init is kept here and nowhere else: `init` is the
+// source of a queued copy, so the stream is synchronised on every path, a
+// failed launch included, before it goes out of scope.
+hipError_t run_select(pbh_engine *e, const PooledSelect &ps, int64_t first, int64_t count,
+                      uint64_t *sel, double *out, double *order_stats) {
+  const int32_t d = e->d;
+  std::vector<uint64_t> init((size_t)(4 * d * pbh::kSelectMaxTargets + d));
+  hipError_t err = pbh::launch_select_init(sel, d, ps.nt, ps.plan.ranks.data(), init.data(),
+                                           e->stream);
+  for (int32_t pass = 0; err == hipSuccess && pass < pbh::select_passes(); ++pass)
+    err = pbh::launch_select_pass(e->tx, e->n, d, first, count, sel, ps.nt, pass, e->stream);
+  const hipError_t drained = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess) err = drained;
+  std::vector<double> order((size_t)d * ps.nt);   // [d][nt]
+  if (err == hipSuccess)
+    err = hipMemcpy(order.data(), sel + pbh::select_stats_offset(d, ps.nt),
+                    order.size() * sizeof(double), hipMemcpyDeviceToHost);
+  if (err == hipSuccess) pbh::pooled_interpolate(ps.plan, d, order.data(), out, order_stats);
+  return err;
+}
+
+// The scores of dim k on the stream: its pooled ranks over the window turned to
+// normal scores z [count][n] in the layout's z (folded about med[k] where med
+// is not null; the rank rows in the layout's r with want_ranks), then, with
+// `rows`, launch_rhat_chain on z as a one-dim trace into the layout's stats.
+hipError_t launch_scores(pbh_engine *e, const pbh::RankLayout &l, int64_t k, int64_t first,
+                         int64_t count, const double *med, bool want_ranks, bool rows) {
+  hipError_t err = pbh::launch_rank_dim(e->tx, e->n, (int32_t)e->d, (int32_t)k, first, count, med,
+                                        e->scratch, l, want_ranks, e->stream);
+  if (err == hipSuccess && rows)
+    err = pbh::launch_rhat_chain(at<const double>(e->scratch, l.z), e->n, 1, 0, count,
+                                 at<double>(e->scratch, l.stats), e->stream);
+  return err;
 }
 
 }  // namespace
@@ -125,15 +187,14 @@ int pbh_trace_expectation(pbh_engine *e, int64_t first, int64_t count,
   HIP_TRY(hipSetDevice(e->device));
   const size_t dn = (size_t)e->d * e->n;
   if (const int rc = scratch(e, dn * sizeof(double))) return rc;
-  double *dout = reinterpret_cast<double *>(e->scratch);
+  double *dout = at<double>(e->scratch, 0);
   hipError_t err = pbh::launch_trace_expectation(
       e->tx, e->tlp, e->n, e->d, first, count, exponent,
       e->k.pscale == PBH_PSCALE_LIN ? 1 : 0, e->k.log_npi, dout, e->stream);
   if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
   if (err == hipSuccess)
     err = hipMemcpy(out, dout, dn * sizeof(double), hipMemcpyDeviceToHost);
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_trace_expectation: %s", hipGetErrorString(err));
+  if (err != hipSuccess) return hip_fail("pbh_trace_expectation", err);
   return PBH_OK;
 }
 
@@ -151,7 +212,7 @@ int pbh_trace_quantile(pbh_engine *e, int64_t first, int64_t count, int32_t nq,
   HIP_TRY(hipSetDevice(e->device));
   const size_t res = (size_t)nq * e->d * e->n;
   if (const int rc = scratch(e, (PBH_QUANTILE_MAX_Q + res) * sizeof(double))) return rc;
-  double *dbuf = reinterpret_cast<double *>(e->scratch);   // q [nq], then the result [nq][d][n]
+  double *dbuf = at<double>(e->scratch, 0);   // q [nq], then the result [nq][d][n]
   hipError_t err = hipMemcpyAsync(dbuf, q, nq * sizeof(double), hipMemcpyHostToDevice,
                                   e->stream);
   if (err == hipSuccess)
@@ -163,8 +224,7 @@ int pbh_trace_quantile(pbh_engine *e, int64_t first, int64_t count, int32_t nq,
   if (err == hipSuccess)
     err = hipMemcpy(out, dbuf + PBH_QUANTILE_MAX_Q, res * sizeof(double),
                     hipMemcpyDeviceToHost);
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_trace_quantile: %s", hipGetErrorString(err));
+  if (err != hipSuccess) return hip_fail("pbh_trace_quantile", err);
   return PBH_OK;
 }
 
@@ -194,8 +254,7 @@ int pbh_trace_rhat(pbh_engine *e, int64_t first, int64_t count, int32_t group,
   // stats [6][d][n], the superchains' (mu, B + W) [2][d][K], the results [2][d]
   const int64_t n_stats = 6 * d * n, n_sc = 2 * d * K, need = n_stats + n_sc + 2 * d;
   if (const int rc = scratch(e, (size_t)need * sizeof(double))) return rc;
-  double *stats = reinterpret_cast<double *>(e->scratch), *sc = stats + n_stats,
-         *res = sc + n_sc;
+  double *stats = at<double>(e->scratch, 0), *sc = stats + n_stats, *res = sc + n_sc;
   hipError_t err = pbh::launch_rhat_chain(e->tx, n, (int32_t)d, first, count, stats, e->stream);
   if (err == hipSuccess && (split_rhat || nested_rhat))
     err = pbh::launch_rhat_cross(stats, n, (int32_t)d, count, group, sc,
@@ -207,8 +266,7 @@ int pbh_trace_rhat(pbh_engine *e, int64_t first, int64_t count, int32_t group,
     err = hipMemcpy(host, res, 2 * d * sizeof(double), hipMemcpyDeviceToHost);
   if (err == hipSuccess && chain_stats)
     err = hipMemcpy(chain_stats, stats, n_stats * sizeof(double), hipMemcpyDeviceToHost);
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_trace_rhat: %s", hipGetErrorString(err));
+  if (err != hipSuccess) return hip_fail("pbh_trace_rhat", err);
   if (split_rhat) std::memcpy(split_rhat, host, d * sizeof(double));
   if (nested_rhat) std::memcpy(nested_rhat, host + d, d * sizeof(double));
   return PBH_OK;
@@ -219,27 +277,12 @@ int pbh_trace_quantile_pooled(pbh_engine *e, int64_t first, int64_t count, int32
   if (const int rc = trace_enter(e, {{q, "q"}, {out, "out"}}, true, first, count, 1,
                                  [&] { return quantile_args(nq, q, count); }))
     return rc;
-  const int64_t n = e->n, d = e->d;
-  const pbh::PooledPlan plan = pbh::pooled_plan(n * count, nq, q);
-  const int32_t nt = (int32_t)plan.ranks.size();
+  const PooledSelect ps(e->n * count, (int32_t)e->d, nq, q);
   HIP_TRY(hipSetDevice(e->device));
-  if (const int rc = scratch(e, (size_t)pbh::select_scratch_words((int32_t)d, nt) *
-                                    sizeof(uint64_t)))
-    return rc;
-  uint64_t *sel = reinterpret_cast<uint64_t *>(e->scratch);
-  std::vector<uint64_t> init((size_t)(4 * d * pbh::kSelectMaxTargets + d));
-  hipError_t err = pbh::launch_select_init(sel, (int32_t)d, nt, plan.ranks.data(), init.data(),
-                                           e->stream);
-  for (int32_t pass = 0; err == hipSuccess && pass < pbh::select_passes(); ++pass)
-    err = pbh::launch_select_pass(e->tx, n, (int32_t)d, first, count, sel, nt, pass, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  std::vector<double> stats((size_t)(d * nt));   // [d][nt]
-  if (err == hipSuccess)
-    err = hipMemcpy(stats.data(), sel + pbh::select_stats_offset((int32_t)d, nt),
-                    stats.size() * sizeof(double), hipMemcpyDeviceToHost);
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_trace_quantile_pooled: %s", hipGetErrorString(err));
-  pbh::pooled_interpolate(plan, d, stats.data(), out, order_stats);
+  if (const int rc = scratch(e, (size_t)ps.words * sizeof(uint64_t))) return rc;
+  const hipError_t err = run_select(e, ps, first, count, at<uint64_t>(e->scratch, 0), out,
+                                    order_stats);
+  if (err != hipSuccess) return hip_fail("pbh_trace_quantile_pooled", err);
   return PBH_OK;
 }
 
@@ -257,63 +300,39 @@ int pbh_trace_rhat_rank(pbh_engine *e, int64_t first, int64_t count, double *bul
   const bool want_ranks = ranks || folded_ranks;
   // the folded variant's fold point: the pooled median, selected for all dims
   const double half = 0.5;
-  pbh::PooledPlan plan;
-  int32_t nt = 0;
-  int64_t sel_words = 0;
-  if (want[1]) {
-    plan = pbh::pooled_plan(n * count, 1, &half);
-    nt = (int32_t)plan.ranks.size();
-    sel_words = pbh::select_scratch_words((int32_t)d, nt);
-  }
+  const PooledSelect ps = want[1] ? PooledSelect(n * count, (int32_t)d, 1, &half) : PooledSelect();
   pbh::RankLayout l;
-  if (!pbh::rank_layout(n, count, (int32_t)d, sel_words, want_ranks, &l))
+  if (!pbh::rank_layout(n, count, (int32_t)d, ps.words, want_ranks, &l))
     return fail(PBH_ERR_UNSUPPORTED, "%lld chains of %lld records: the pooled sort indexes "
                 "fewer than 2^32 elements per dim", (long long)n, (long long)count);
   HIP_TRY(hipSetDevice(e->device));
   if (const int rc = scratch(e, (size_t)l.bytes)) return rc;
+  if (const int rc = want[1] ? stage(e, (size_t)d) : PBH_OK) return rc;
   unsigned char *sc = e->scratch;
-  double *med = reinterpret_cast<double *>(sc + l.med);
-  double *res = reinterpret_cast<double *>(sc + l.res);
-  double *stats = reinterpret_cast<double *>(sc + l.stats);
-  const double *z = reinterpret_cast<const double *>(sc + l.z);
-  const double *r = reinterpret_cast<const double *>(sc + l.r);
+  double *med = at<double>(sc, l.med), *res = at<double>(sc, l.res);
   hipError_t err = hipSuccess;
-  double host_med[PBH_MAX_DIM];   // (alive until the stream has been synchronised)
   if (want[1]) {
-    uint64_t *sel = reinterpret_cast<uint64_t *>(sc + l.select);
-    std::vector<uint64_t> init((size_t)(4 * d * pbh::kSelectMaxTargets + d));
-    err = pbh::launch_select_init(sel, (int32_t)d, nt, plan.ranks.data(), init.data(), e->stream);
-    for (int32_t pass = 0; err == hipSuccess && pass < pbh::select_passes(); ++pass)
-      err = pbh::launch_select_pass(e->tx, n, (int32_t)d, first, count, sel, nt, pass, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    std::vector<double> order((size_t)(d * nt));   // [d][nt]
+    // the median [d] through the pinned stage, which outlives the queued copy
+    err = run_select(e, ps, first, count, at<uint64_t>(sc, l.select), e->stage, nullptr);
     if (err == hipSuccess)
-      err = hipMemcpy(order.data(), sel + pbh::select_stats_offset((int32_t)d, nt),
-                      order.size() * sizeof(double), hipMemcpyDeviceToHost);
-    if (err == hipSuccess) {
-      pbh::pooled_interpolate(plan, d, order.data(), host_med, nullptr);
-      err = hipMemcpyAsync(med, host_med, d * sizeof(double), hipMemcpyHostToDevice, e->stream);
-    }
+      err = hipMemcpyAsync(med, e->stage, d * sizeof(double), hipMemcpyHostToDevice, e->stream);
   }
   for (int v = 0; v < 2; ++v) {
     if (!want[v]) continue;
     double *out_ranks = v ? folded_ranks : ranks;
     const bool reduce = v ? folded != nullptr : bulk != nullptr;
     for (int64_t k = 0; err == hipSuccess && k < d; ++k) {
-      err = pbh::launch_rank_dim(e->tx, n, (int32_t)d, (int32_t)k, first, count,
-                                 v ? med : nullptr, sc, l, out_ranks != nullptr, e->stream);
+      err = launch_scores(e, l, k, first, count, v ? med : nullptr, out_ranks != nullptr, reduce);
       if (err == hipSuccess && reduce)
-        err = pbh::launch_rhat_chain(z, n, 1, 0, count, stats, e->stream);
-      if (err == hipSuccess && reduce)
-        err = pbh::launch_rhat_cross(stats, n, 1, count, 0, nullptr, res + v * d + k, nullptr,
-                                     e->stream);
+        err = pbh::launch_rhat_cross(at<double>(sc, l.stats), n, 1, count, 0, nullptr,
+                                     res + v * d + k, nullptr, e->stream);
       if (err == hipSuccess && out_ranks) {
         // the dim's [count][n] into the host's [count][d][n]
         err = hipStreamSynchronize(e->stream);
         if (err == hipSuccess)
-          err = hipMemcpy2D(out_ranks + k * n, (size_t)(d * n) * sizeof(double), r,
-                            (size_t)n * sizeof(double), (size_t)n * sizeof(double),
-                            (size_t)count, hipMemcpyDeviceToHost);
+          err = hipMemcpy2D(out_ranks + k * n, (size_t)(d * n) * sizeof(double),
+                            at<const double>(sc, l.r), (size_t)n * sizeof(double),
+                            (size_t)n * sizeof(double), (size_t)count, hipMemcpyDeviceToHost);
       }
     }
   }
@@ -321,8 +340,7 @@ int pbh_trace_rhat_rank(pbh_engine *e, int64_t first, int64_t count, double *bul
   double host[2 * PBH_MAX_DIM];
   if (err == hipSuccess && (bulk || folded))
     err = hipMemcpy(host, res, 2 * d * sizeof(double), hipMemcpyDeviceToHost);
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_trace_rhat_rank: %s", hipGetErrorString(err));
+  if (err != hipSuccess) return hip_fail("pbh_trace_rhat_rank", err);
   if (bulk) std::memcpy(bulk, host, d * sizeof(double));
   if (folded) std::memcpy(folded, host + d, d * sizeof(double));
   return PBH_OK;
@@ -351,56 +369,36 @@ int pbh_trace_ess_rank(pbh_engine *e, int64_t first, int64_t count, double *bulk
                 "fewer than 2^32 elements per dim", (long long)n, (long long)count);
   // the tail's thresholds: the pooled 5 % and 95 % quantiles, selected for all dims
   const double q_tail[2] = {0.05, 0.95};
-  pbh::PooledPlan plan;
-  int32_t nt = 0;
-  int64_t sel_words = 0;
-  if (want_tail) {
-    plan = pbh::pooled_plan(n * count, 2, q_tail);
-    nt = (int32_t)plan.ranks.size();
-    sel_words = pbh::select_scratch_words((int32_t)d, nt);
-  }
+  const PooledSelect ps = want_tail ? PooledSelect(n * count, (int32_t)d, 2, q_tail) : PooledSelect();
   pbh::EssLayout l;
-  if (!pbh::ess_layout(n, count, (int32_t)d, want[0] ? rl.bytes : 0, sel_words, &l))
+  if (!pbh::ess_layout(n, count, (int32_t)d, want[0] ? rl.bytes : 0, ps.words, &l))
     return fail(PBH_ERR_ARG, "pbh_trace_ess_rank: no scratch layout for %lld chains of %lld "
                 "records", (long long)n, (long long)count);
   HIP_TRY(hipSetDevice(e->device));
   if (const int rc = scratch(e, (size_t)l.bytes)) return rc;
+  if (const int rc = want_tail ? stage(e, (size_t)(2 * d)) : PBH_OK) return rc;
   unsigned char *sc = e->scratch;
-  double *thr = reinterpret_cast<double *>(sc + l.thr);
-  double *part = reinterpret_cast<double *>(sc + l.part);
-  double *acov = reinterpret_cast<double *>(sc + l.acov);     // [4][d][h]
-  double *means = reinterpret_cast<double *>(sc + l.means);   // [4][2][d][n]
-  double *stats = reinterpret_cast<double *>(sc + l.stats);   // [6][d][n]
+  double *thr = at<double>(sc, l.thr), *part = at<double>(sc, l.part);
+  double *acov = at<double>(sc, l.acov);     // [4][d][h]
+  double *means = at<double>(sc, l.means);   // [4][2][d][n]
+  double *stats = at<double>(sc, l.stats);   // [6][d][n]
   const size_t row = (size_t)n * sizeof(double);
   const auto mean_at = [&](int v, int half, int64_t k) { return means + ((v * 2 + half) * d + k) * n; };
   hipError_t err = hipSuccess;
-  double host_thr[2 * PBH_MAX_DIM];   // (alive until the stream has been synchronised)
   if (want_tail) {
-    uint64_t *sel = reinterpret_cast<uint64_t *>(sc + l.select);
-    std::vector<uint64_t> init((size_t)(4 * d * pbh::kSelectMaxTargets + d));
-    err = pbh::launch_select_init(sel, (int32_t)d, nt, plan.ranks.data(), init.data(), e->stream);
-    for (int32_t pass = 0; err == hipSuccess && pass < pbh::select_passes(); ++pass)
-      err = pbh::launch_select_pass(e->tx, n, (int32_t)d, first, count, sel, nt, pass, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    std::vector<double> order((size_t)(d * nt));   // [d][nt]
+    // the thresholds [2][d] through the pinned stage, which outlives the queued copy
+    err = run_select(e, ps, first, count, at<uint64_t>(sc, l.select), e->stage, nullptr);
     if (err == hipSuccess)
-      err = hipMemcpy(order.data(), sel + pbh::select_stats_offset((int32_t)d, nt),
-                      order.size() * sizeof(double), hipMemcpyDeviceToHost);
-    if (err == hipSuccess) {
-      pbh::pooled_interpolate(plan, d, order.data(), host_thr, nullptr);   // [2][d]
-      err = hipMemcpyAsync(thr, host_thr, 2 * d * sizeof(double), hipMemcpyHostToDevice,
+      err = hipMemcpyAsync(thr, e->stage, 2 * d * sizeof(double), hipMemcpyHostToDevice,
                            e->stream);
-    }
   }
   if (want[0]) {
     // per dim: the scores z [count][n] as a one-dim trace, their half means
     // from rhat_chain's rows
-    const double *z = reinterpret_cast<const double *>(sc + rl.z);
-    double *zstats = reinterpret_cast<double *>(sc + rl.stats);   // [6][n]
+    const double *z = at<const double>(sc, rl.z);
+    const double *zstats = at<const double>(sc, rl.stats);   // [6][n]
     for (int64_t k = 0; err == hipSuccess && k < d; ++k) {
-      err = pbh::launch_rank_dim(e->tx, n, (int32_t)d, (int32_t)k, first, count, nullptr, sc, rl,
-                                 false, e->stream);
-      if (err == hipSuccess) err = pbh::launch_rhat_chain(z, n, 1, 0, count, zstats, e->stream);
+      err = launch_scores(e, rl, k, first, count, nullptr, false, true);
       if (err == hipSuccess)
         err = pbh::launch_ess_spectrum(z, n, n, count, nullptr, l, part, nullptr, nullptr,
                                        e->stream);
@@ -447,11 +445,7 @@ int pbh_trace_ess_rank(pbh_engine *e, int64_t first, int64_t count, double *bulk
     }
     if (mean_acov) std::memcpy(mean_acov + v * d * h, hA.data(), hA.size() * sizeof(double));
   }
-  if (err != hipSuccess) {
-    // (host_thr's copy may still be queued: it must not outlive this frame)
-    (void)hipStreamSynchronize(e->stream);
-    return fail(PBH_ERR_HIP, "pbh_trace_ess_rank: %s", hipGetErrorString(err));
-  }
+  if (err != hipSuccess) return hip_fail("pbh_trace_ess_rank", err);
   if (bulk) std::memcpy(bulk, ess[0], d * sizeof(double));
   if (basic) std::memcpy(basic, ess[3], d * sizeof(double));
   if (tail_parts) {
@@ -479,11 +473,11 @@ int pbh_trace_ess(pbh_engine *e, int64_t first, int64_t count, double *ess) {
   if (ess) {
     // through a pinned staging buffer: a pageable copy of the 512 KB cfg5
     // result was ~0.1 ms of the call
-    if (const int rc = ess_host(e, dn)) return rc;
-    HIP_TRY(hipMemcpyAsync(e->ess_host, e->ess, dn * sizeof(double), hipMemcpyDeviceToHost,
+    if (const int rc = stage(e, dn)) return rc;
+    HIP_TRY(hipMemcpyAsync(e->stage, e->ess, dn * sizeof(double), hipMemcpyDeviceToHost,
                            e->stream));
     HIP_TRY(pbh::stream_wait(e));
-    std::memcpy(ess, e->ess_host, dn * sizeof(double));
+    std::memcpy(ess, e->stage, dn * sizeof(double));
   }
   return PBH_OK;
 }
@@ -493,16 +487,16 @@ int pbh_trace_ess_total(pbh_engine *e, int64_t first, int64_t count, double *tot
   // the per-chain ESS on the device (no copy), then the per-dim sums
   if (const int rc = pbh_trace_ess(e, first, count, nullptr)) return rc;
   const int d = e->d;
-  if (const int rc = ess_host(e, d)) return rc;
+  if (const int rc = stage(e, d)) return rc;
   // the totals land in the scalar scratch (d doubles, allocated lazily)
   if (!e->ess_tot) {
     if (const int rc = pbh::dalloc(e->ess_tot, PBH_MAX_DIM)) return rc;
   }
   HIP_TRY(pbh::launch_ess_total(e->ess, e->n, d, e->ess_tot, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->ess_host, e->ess_tot, d * sizeof(double), hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(e->stage, e->ess_tot, d * sizeof(double), hipMemcpyDeviceToHost,
                          e->stream));
   HIP_TRY(pbh::stream_wait(e));
-  std::memcpy(total, e->ess_host, d * sizeof(double));
+  std::memcpy(total, e->stage, d * sizeof(double));
   return PBH_OK;
 }
 

@@ -3,9 +3,9 @@
 // host steps of the pooled quantile around the device's radix select, and the
 // geometry and scratch layout of the pooled sort (pbh_rank.hip), and the layout
 // and the estimator of the ESS across chains (pbh_ess_rank.hip).  No HIP: a host
-// compiler alone builds it (tests/trace_host_main.cpp, rank_host_main.cpp,
-// ess_host_main.cpp).  Built with -ffp-contract=off: the interpolation and the
-// estimator must round as NumPy's do.
+// compiler alone builds it (tests/trace_host_main.cpp, the one program the CPU
+// tests drive it through).  Built with -ffp-contract=off: the interpolation and
+// the estimator must round as NumPy's do.
 #pragma once
 #include <stdint.h>
 

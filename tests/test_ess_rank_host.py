@@ -12,23 +12,18 @@ printed.  Every decision of Geyer's scan must be
 clear of rounding (ess_reference.clear), which is asserted, not assumed.
 
 And pbh_trace_host.cpp's multi_chain_ess and ess_layout, driven by the
-stand-alone program tests/ess_host_main.cpp built with a host compiler alone,
+stand-alone program tests/trace_host_main.cpp built with a host compiler alone,
 -ffp-contract=off and the address and undefined-behaviour sanitizers, and run
-as a child process: its ESS equals diag.multi_chain_ess bit for bit on the same
+as a child process (host_program.py): its ESS equals diag.multi_chain_ess bit for bit on the same
 means and autocovariances, and the scratch geometry is right at the edges."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 from probayes_amd import diag
+from host_program import hex_words, host
 from ess_reference import VARIANTS, clear, ref_acov, ref_ess, ref_rank_ess
 from rhat_reference import EPS, ar1_with_repeats, rel_dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'probayes_amd', 'csrc')
 BOUND = 64 * EPS
 BOUND_H2_INDICATOR = 512 * EPS   # (see above; never above 1e-9)
 assert BOUND <= BOUND_H2_INDICATOR <= 1e-9
@@ -162,47 +157,6 @@ def test_argument_checks():
 
 
 # ---- the host stage of the library, through the stand-alone program ---------
-def _compiler():
-  for name in ('c++', 'g++', 'clang++', '/opt/rocm/lib/llvm/bin/clang++'):
-    path = shutil.which(name)
-    if path:
-      return path
-  return None
-
-
-@pytest.fixture(scope='module')
-def host(tmp_path_factory):
-  """run(lines) -> the program's answers, one per request line"""
-  cxx = _compiler()
-  if cxx is None:
-    pytest.skip('no host C++ compiler')
-  tmp = tmp_path_factory.mktemp('ess_host')
-  exe = str(tmp / 'ess_host_main')
-  # the sanitizer runtimes linked into the program (clang's default), so that
-  # it runs whatever else the loader brings in first
-  version = subprocess.run([cxx, '--version'], capture_output=True, text=True).stdout
-  static = [] if 'clang' in version else ['-static-libasan', '-static-libubsan']
-  subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-Wall', '-ffp-contract=off',
-                         '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                        [os.path.join(ROOT, 'tests', 'ess_host_main.cpp'),
-                         os.path.join(CSRC, 'pbh_trace_host.cpp'), '-o', exe])
-
-  def run(lines):
-    req = tmp / 'requests.txt'
-    req.write_text(''.join(l + '\n' for l in lines))
-    r = subprocess.run([exe, str(req)], capture_output=True, text=True)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    out = r.stdout.splitlines()
-    assert len(out) == len(lines)
-    return out
-  return run
-
-
-def _hex(a):
-  return ' '.join('{:016x}'.format(int(b)) for b in
-                  np.ascontiguousarray(a, np.float64).reshape(-1).view(np.uint64))
-
-
 def _same_bits(a, b):
   return (np.isnan(a) and np.isnan(b)) or np.float64(a).tobytes() == np.float64(b).tobytes()
 
@@ -232,7 +186,7 @@ def _host_inputs():
 
 def test_host_stage_equals_diag_bit_for_bit(host):
   inputs = _host_inputs()
-  lines = ['ess {} {} {} {}'.format(m.size, a.size, _hex(m), _hex(a)) for _, m, a in inputs]
+  lines = ['ess {} {} {} {}'.format(m.size, a.size, hex_words(m), hex_words(a)) for _, m, a in inputs]
   seen_full = seen_nan = seen_stop = False
   for (label, m, a), ans in zip(inputs, host(lines)):
     word = ans.split()
@@ -267,10 +221,10 @@ def test_layout_geometry_and_refusals(host):
   shapes = [(1, 4, 1, 0, 0), (1, 4, 1, 1, 9), (2, 5, 3, 1, 100), (33, 37, 2, 1, 100),
             (2004, 119, 10, 1, 100), (2 * most, 4096, 2, 0, 7), (2 * most + 1, 4097, 2, 1, 7),
             (33000, 16, 2, 1, 50), (2**20, 4096, 32, 0, 1000)]
-  lines = ['layout {} {} {} {} {}'.format(*s) for s in shapes]
-  lines += ['layout 8 4098 2 1 0', 'layout 8 3 2 1 0', 'layout 0 8 2 0 0', 'layout 8 8 0 0 0',
-            'layout 8 8 2 0 -1', 'layout {} 4096 1 1 0'.format(2**20),
-            'layout {} 4096 1 0 0'.format(2**20)]
+  lines = ['ess_layout {} {} {} {} {}'.format(*s) for s in shapes]
+  lines += ['ess_layout 8 4098 2 1 0', 'ess_layout 8 3 2 1 0', 'ess_layout 0 8 2 0 0',
+            'ess_layout 8 8 0 0 0', 'ess_layout 8 8 2 0 -1', 'ess_layout {} 4096 1 1 0'.format(2**20),
+            'ess_layout {} 4096 1 0 0'.format(2**20)]
   ans = [_layout(a) for a in host(lines)]
   for (n, count, d, bulk, sel), l in zip(shapes, ans):
     assert isinstance(l, dict), (n, count, l)

@@ -9,7 +9,6 @@ it must accept every example density.  The leaves fix the order of NumPy's
 pairwise sum: summing in their order must give np.sum's bits."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -20,6 +19,7 @@ from probayes_amd import expr
 import expr_programs
 from expr_examples import EXPR_WORKLOADS
 from expr_data_examples import DATA_WORKLOADS
+from host_program import compiler as _compiler
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'probayes_amd', 'csrc')
@@ -27,14 +27,6 @@ LEAF_STACK = 12        # kExprLeafStack (pbh_expr_words.h)
 N_OBS = [1, 7, 8, 9, 127, 128, 129, 136, 137, 255, 256, 257, 300, 1000, 4097, 65536]
 # np.sum adds the pairwise sums of buffers of 8192 elements one after another
 N_OBS += [8192, 8193, 50000]
-
-
-def _compiler():
-  for name in ('c++', 'g++', 'clang++', '/opt/rocm/lib/llvm/bin/clang++'):
-    path = shutil.which(name)
-    if path:
-      return path
-  return None
 
 
 @pytest.fixture(scope='module')

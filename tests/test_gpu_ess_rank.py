@@ -21,8 +21,6 @@ d = 2; N = 33 with an odd count (a last chain without a partner, dims that do
 not start on a 16-byte boundary); N = 6 and N = 1; T = 4 098 of slow chains for
 h = 2 048, the whole transform; chains that never move; a NaN."""
 import functools
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -33,16 +31,11 @@ from probayes_amd import diag
 from probayes_amd._lib import PbhError
 from ess_reference import VARIANTS, clear, ref_rank_ess
 from rhat_reference import rel_dist
-from test_gpu_pooled_quantile import Q64, _tied_starts
-from trace_helpers import check_no_side_effects, run
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from trace_helpers import (N_BIG, Q64, T_BIG, WINDOWS, big_run, check_no_side_effects, flat,
+                           run, sampler_block, tied_starts)
 
 pytestmark = pytest.mark.gpu
 
-N_BIG, T_BIG = 2004, 160
-WINDOWS = [(40, 120), (40, 119), (0, 4)]
 KEYS = VARIANTS + ('tail',)
 LD = np.longdouble
 
@@ -113,21 +106,17 @@ def _same(a, b):
       assert a[k].tobytes() == b[k].tobytes(), k
 
 
-@functools.lru_cache(maxsize=None)
+def _everything_twice_then_the_defaults(eng, first, count):
+  return (eng.trace_ess_rank(first, count, basic=True, acov=True),
+          eng.trace_ess_rank(first, count, basic=True, acov=True),
+          eng.trace_ess_rank(first, count))
+
+
 def _big(name):
   """One run per model: the host copy of the trace and every device result,
   each asked for twice, and once with the default outputs only."""
-  spec = oracle.golden_spec(name)
-  eng = run(spec, golden_init(name, N_BIG), T_BIG)
-  try:
-    x = eng.trace()['v_x']
-    dev, again, plain = {}, {}, {}
-    for first, count in WINDOWS:
-      dev[first, count] = eng.trace_ess_rank(first, count, basic=True, acov=True)
-      again[first, count] = eng.trace_ess_rank(first, count, basic=True, acov=True)
-      plain[first, count] = eng.trace_ess_rank(first, count)
-  finally:
-    eng.close()
+  spec, x, res = big_run(name, _everything_twice_then_the_defaults)
+  dev, again, plain = ({w: r[i] for w, r in res.items()} for i in range(3))
   return spec, x, dev, again, plain
 
 
@@ -285,7 +274,7 @@ def test_constant_chains(kind):
   a finite value."""
   base = oracle.golden_spec('gmm2')
   spec = dict(base, proposal=dict(base['proposal'], scale=np.zeros(2)))
-  x0 = _tied_starts(kind)
+  x0 = tied_starts(kind)
   eng = run(spec, x0, 12)
   try:
     x = eng.trace()['v_x']
@@ -345,13 +334,6 @@ def test_no_side_effects():
   check_no_side_effects(reduce, 516)
 
 
-def _flat(res):
-  """every array of a result, in a fixed order"""
-  if isinstance(res, dict):
-    return [a for k in sorted(res) if res[k] is not None for a in _flat(res[k])]
-  return list(res) if isinstance(res, tuple) else [res]
-
-
 def test_results_do_not_depend_on_what_the_scratch_held():
   """Two engines with one seed make the same calls on the shared reduction
   scratch, one in this order and one in reverse: the same bits."""
@@ -375,7 +357,7 @@ def test_results_do_not_depend_on_what_the_scratch_held():
   a, b = got
   assert np.array_equal(traces[0], traces[1])
   for name, _ in calls:
-    fa, fb = _flat(a[name]), _flat(b[name])
+    fa, fb = flat(a[name]), flat(b[name])
     assert len(fa) == len(fb) > 0, name
     for u, v in zip(fa, fb):
       assert u.shape == v.shape and u.tobytes() == v.tobytes(), name
@@ -414,20 +396,8 @@ def test_refusals_leave_the_engine_working():
 
 
 def test_sampler_trace_ess_rank():
-  import probayes_amd as pb
-  from mcmc_examples import WORKLOADS
-  builder, params, _, _, _ = WORKLOADS['metrohast_norm1d']
-  g = oracle.load_golden('metrohast_norm1d')
-  params = oracle.workloads.golden_params(g) if params else params
-  process, init, extra, kwds, keys = builder(pb, params)
   n, t = 68, 96
-  sampler = process.sampler(init, extra, stop=t, chains=n, rng='philox', seed=7, **kwds)
-  try:
-    samples = process.walk(sampler)
-    assert len(samples) == t
-    v = process(samples).v
-    x = np.stack([np.asarray(v[k]).T for k in keys], axis=2)   # [n, t, d]
-    assert x.shape == (n, t, len(keys))
+  with sampler_block(n, t) as (sampler, process, x, keys, _):
     names = ('bulk', 'tail', 'tail_lower', 'tail_upper')
     for kw, (first, count) in ((dict(first=8, count=87), (8, 87)), (dict(), (0, t))):
       got = sampler.trace_ess_rank(**kw)
@@ -450,5 +420,3 @@ def test_sampler_trace_ess_rank():
     process.next(sampler)
     with pytest.raises(ValueError, match='another block'):
       sampler.trace_ess_rank()
-  finally:
-    sampler.close()

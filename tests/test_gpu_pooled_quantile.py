@@ -20,10 +20,6 @@ chains): one value everywhere; a np.nextafter ladder from 1.0 (only the last
 digit decides); starts that differ in the top bits only.  The engine accepts
 a NaN start and the chain stays there, so the NaN rule runs on the device too.
 """
-import functools
-import os
-import sys
-
 import numpy as np
 import pytest
 
@@ -31,18 +27,13 @@ import oracle
 from oracle.workloads import golden_init
 from probayes_amd import diag
 from probayes_amd._lib import PbhError
-from trace_helpers import check_no_side_effects, run
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from trace_helpers import (N_BIG, Q64, QS, T_BIG, big_run, check_no_side_effects, run,
+                           sampler_block, tied_starts)
 
 pytestmark = pytest.mark.gpu
 
-QS = [0, 1e-9, .025, .25, 1 / 3, .5, .75, .975, 1 - 1e-9, 1]
-Q64 = list(np.linspace(0., 1., 64))
 QSETS = {'qs': QS, 'one': [.5], 'q64': Q64}
-N_BIG, T_BIG = 2004, 160
-WINDOWS = [(40, 120), (40, 119), (0, 1)]
+WINDOWS = ((40, 120), (40, 119), (0, 1))
 
 
 def _order_stats(x, q, first, count):
@@ -63,21 +54,17 @@ def _exact(what, got, x, q, first, count, equal_nan=False):
   assert np.array_equal(stats, _order_stats(x, q, first, count), equal_nan=equal_nan), what
 
 
-@functools.lru_cache(maxsize=None)
+def _every_list_twice(eng, first, count):
+  return {key: [eng.trace_quantile_pooled(q, first, count, order_stats=True) for _ in range(2)]
+          for key, q in QSETS.items()}
+
+
 def _big(name):
   """One run per model: the host copy of the trace and every device result,
   each asked for twice."""
-  spec = oracle.golden_spec(name)
-  eng = run(spec, golden_init(name, N_BIG), T_BIG)
-  try:
-    x = eng.trace()['v_x']
-    dev, again = {}, {}
-    for first, count in WINDOWS:
-      for key, q in QSETS.items():
-        dev[first, count, key] = eng.trace_quantile_pooled(q, first, count, order_stats=True)
-        again[first, count, key] = eng.trace_quantile_pooled(q, first, count, order_stats=True)
-  finally:
-    eng.close()
+  spec, x, res = big_run(name, _every_list_twice, WINDOWS)
+  dev, again = ({(first, count, key): r[key][i] for (first, count), r in res.items()
+                 for key in QSETS} for i in range(2))
   return spec, x, dev, again
 
 
@@ -127,36 +114,11 @@ def test_few_chains(name):
     eng.close()
 
 
-def _ladder(n):
-  v = np.empty(n)
-  v[0] = 1.
-  for i in range(1, n):
-    v[i] = np.nextafter(v[i - 1], 2.)
-  return v
-
-
-TOP = np.array([1e300, -1e300, 1e-300, -1e-300, 5e-324, 0., -0., -5e-324, 3., -3., 1e300,
-                -1e-300, 0.])
-
-
-def _tied_starts(kind):
-  if kind == 'one_value':
-    return np.repeat(np.array([[-1., 0.5]]), 130, axis=0)
-  if kind == 'last_ulps':
-    lad = _ladder(130)
-    # dim 0 climbs through 130 neighbours of 1.0; dim 1 holds 5 of them, 26 times each
-    return np.stack([lad[np.random.default_rng(1).permutation(130)], -lad[np.arange(130) % 5]],
-                    axis=1)
-  assert kind == 'top_bits'
-  a = np.resize(TOP, 130)
-  return np.stack([a, np.resize(TOP[::-1], 130)], axis=1)
-
-
 @pytest.mark.parametrize('kind', ['one_value', 'last_ulps', 'top_bits'])
 def test_ties_and_every_digit(kind):
   base = oracle.golden_spec('gmm2')
   spec = dict(base, proposal=dict(base['proposal'], scale=np.zeros(2)))
-  x0 = _tied_starts(kind)
+  x0 = tied_starts(kind)
   eng = run(spec, x0, 12)
   try:
     x = eng.trace()['v_x']
@@ -250,18 +212,8 @@ def test_refusals_leave_the_engine_working():
 
 
 def test_sampler_trace_quantile_pooled():
-  import probayes_amd as pb
-  from mcmc_examples import WORKLOADS
-  builder, params, _, _, _ = WORKLOADS['metrohast_norm1d']
-  g = oracle.load_golden('metrohast_norm1d')
-  params = oracle.workloads.golden_params(g) if params else params
-  process, init, extra, kwds, keys = builder(pb, params)
   n, t = 67, 96
-  sampler = process.sampler(init, extra, stop=t, chains=n, rng='philox', seed=7, **kwds)
-  try:
-    samples = process.walk(sampler)
-    assert len(samples) == t
-    v = process(samples).v
+  with sampler_block(n, t) as (sampler, process, _, keys, v):
     got = sampler.trace_quantile_pooled(QS)
     assert set(got) == set(keys)
     for k in keys:
@@ -279,5 +231,3 @@ def test_sampler_trace_quantile_pooled():
     process.next(sampler)
     with pytest.raises(ValueError, match='another block'):
       sampler.trace_quantile_pooled(QS)
-  finally:
-    sampler.close()

@@ -19,7 +19,7 @@ from oracle.workloads import golden_init
 from probayes_amd._lib import PbhError
 from probayes_amd.pd import PD
 from probayes_amd.pscales import rescale
-from trace_helpers import check_no_side_effects, run
+from trace_helpers import check_no_side_effects, run, sampler_block
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -243,18 +243,8 @@ def test_trace_quantile_between_server_commands(monkeypatch):
 
 # ---- the facade --------------------------------------------------------------
 def test_sampler_trace_quantile():
-  import probayes_amd as pb
-  from mcmc_examples import WORKLOADS
-  builder, params, _, _, _ = WORKLOADS['metrohast_norm1d']
-  g = oracle.load_golden('metrohast_norm1d')
-  params = oracle.workloads.golden_params(g) if params else params
-  process, init, extra, kwds, keys = builder(pb, params)
   n, t, qs = 67, 96, [0.05, 0.5, 0.95]
-  sampler = process.sampler(init, extra, stop=t, chains=n, rng='philox', seed=7, **kwds)
-  try:
-    samples = process.walk(sampler)
-    assert len(samples) == t
-    v = process(samples).v
+  with sampler_block(n, t) as (sampler, process, _, keys, v):
     dev_u = sampler.trace_quantile(qs, weighted=False)
     dev_w = sampler.trace_quantile(qs, weighted=True)
     one = sampler.trace_quantile(0.5, weighted=False)
@@ -275,5 +265,3 @@ def test_sampler_trace_quantile():
     process.next(sampler)
     with pytest.raises(ValueError, match='another block'):
       sampler.trace_quantile(qs)
-  finally:
-    sampler.close()

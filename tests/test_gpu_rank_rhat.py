@@ -18,10 +18,6 @@ element tile, tens of tiles, the rejected steps as ties); d = 10 and d = 2; N =
 that never move for ties and every digit; and test_many_elements for more
 tiles than one chunk of the scan holds.
 """
-import functools
-import os
-import sys
-
 import numpy as np
 import pytest
 
@@ -31,16 +27,10 @@ from probayes_amd import diag
 from probayes_amd._lib import PbhError
 from rank_reference import ref_rank_rhat, ref_ranks
 from rhat_reference import device_bound, rel_dist
-from test_gpu_pooled_quantile import Q64, _tied_starts
-from trace_helpers import check_no_side_effects, run
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from trace_helpers import (N_BIG, Q64, T_BIG, WINDOWS, big_run, check_no_side_effects, flat,
+                           run, sampler_block, tied_starts)
 
 pytestmark = pytest.mark.gpu
-
-N_BIG, T_BIG = 2004, 160
-WINDOWS = [(40, 120), (40, 119), (0, 4)]
 
 
 def _median(x, first, count):
@@ -73,21 +63,16 @@ def _close_rhat(what, got, x, first, count):
   return host
 
 
-@functools.lru_cache(maxsize=None)
+def _with_ranks_twice_then_without(eng, first, count):
+  return (eng.trace_rhat_rank(first, count, ranks=True),
+          eng.trace_rhat_rank(first, count, ranks=True), eng.trace_rhat_rank(first, count))
+
+
 def _big(name):
   """One run per model: the host copy of the trace and every device result,
   each asked for twice, and once without the ranks."""
-  spec = oracle.golden_spec(name)
-  eng = run(spec, golden_init(name, N_BIG), T_BIG)
-  try:
-    x = eng.trace()['v_x']
-    dev, again, plain = {}, {}, {}
-    for first, count in WINDOWS:
-      dev[first, count] = eng.trace_rhat_rank(first, count, ranks=True)
-      again[first, count] = eng.trace_rhat_rank(first, count, ranks=True)
-      plain[first, count] = eng.trace_rhat_rank(first, count)
-  finally:
-    eng.close()
+  spec, x, res = big_run(name, _with_ranks_twice_then_without)
+  dev, again, plain = ({w: r[i] for w, r in res.items()} for i in range(3))
   return spec, x, dev, again, plain
 
 
@@ -166,7 +151,7 @@ def test_ties_and_every_digit(kind):
   denormals and both zeros let the top digits decide."""
   base = oracle.golden_spec('gmm2')
   spec = dict(base, proposal=dict(base['proposal'], scale=np.zeros(2)))
-  x0 = _tied_starts(kind)
+  x0 = tied_starts(kind)
   eng = run(spec, x0, 12)
   try:
     x = eng.trace()['v_x']
@@ -237,13 +222,6 @@ def test_no_side_effects():
   check_no_side_effects(reduce, 516)
 
 
-def _flat(res):
-  """every array of a result, in a fixed order"""
-  if isinstance(res, dict):
-    return [res[k] for k in sorted(res) if res[k] is not None]
-  return list(res) if isinstance(res, tuple) else [res]
-
-
 def test_results_do_not_depend_on_what_the_scratch_held():
   """Two engines with one seed make the same four calls on the shared
   reduction scratch, one in this order and one in reverse: the same bits."""
@@ -266,7 +244,7 @@ def test_results_do_not_depend_on_what_the_scratch_held():
   a, b = got
   assert np.array_equal(traces[0], traces[1])
   for name, _ in calls:
-    fa, fb = _flat(a[name]), _flat(b[name])
+    fa, fb = flat(a[name]), flat(b[name])
     assert len(fa) == len(fb) > 0, name
     for u, v in zip(fa, fb):
       assert u.shape == v.shape and u.tobytes() == v.tobytes(), name
@@ -308,20 +286,8 @@ def test_refusals_leave_the_engine_working():
 
 
 def test_sampler_trace_rhat_rank():
-  import probayes_amd as pb
-  from mcmc_examples import WORKLOADS
-  builder, params, _, _, _ = WORKLOADS['metrohast_norm1d']
-  g = oracle.load_golden('metrohast_norm1d')
-  params = oracle.workloads.golden_params(g) if params else params
-  process, init, extra, kwds, keys = builder(pb, params)
   n, t = 68, 96
-  sampler = process.sampler(init, extra, stop=t, chains=n, rng='philox', seed=7, **kwds)
-  try:
-    samples = process.walk(sampler)
-    assert len(samples) == t
-    v = process(samples).v
-    x = np.stack([np.asarray(v[k]).T for k in keys], axis=2)   # [n, t, d]
-    assert x.shape == (n, t, len(keys))
+  with sampler_block(n, t) as (sampler, process, x, keys, _):
     got = sampler.trace_rhat_rank(8, 87)
     assert set(got) == {'bulk', 'folded', 'rhat'} and set(got['rhat']) == set(keys)
     _close_rhat('sampler', {k: np.array([got[k][name] for name in keys]) for k in got}, x, 8, 87)
@@ -335,5 +301,3 @@ def test_sampler_trace_rhat_rank():
     process.next(sampler)
     with pytest.raises(ValueError, match='another block'):
       sampler.trace_rhat_rank()
-  finally:
-    sampler.close()

@@ -24,8 +24,6 @@ leaves every chain at its start (the golden specs have no uniform delta; this
 is their equivalent).
 """
 import functools
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -35,33 +33,23 @@ from oracle.workloads import golden_init
 from probayes_amd import diag
 from probayes_amd._lib import PbhError
 from rhat_reference import device_bound, ref_moments, ref_nested, ref_split, rel_dist
-from trace_helpers import check_no_side_effects, run
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from trace_helpers import N_BIG, WINDOWS, big_run, check_no_side_effects, run, sampler_block
 
 pytestmark = pytest.mark.gpu
 
-N_BIG, T_BIG = 2004, 160
-WINDOWS = [(40, 120), (40, 119), (0, 4)]
 GROUPS = [1, 4, 12, 167, N_BIG // 2]
 
 
-@functools.lru_cache(maxsize=None)
+def _every_group_twice(eng, first, count):
+  return {g: [eng.trace_rhat(first, count, g, stats=True) for _ in range(2)] for g in GROUPS}
+
+
 def _big(name):
   """One run per model: the host copy of the trace and every device result,
   each asked for twice."""
-  spec = oracle.golden_spec(name)
-  eng = run(spec, golden_init(name, N_BIG), T_BIG)
-  try:
-    x = eng.trace()['v_x']
-    dev, again = {}, {}
-    for first, count in WINDOWS:
-      for g in GROUPS:
-        dev[first, count, g] = eng.trace_rhat(first, count, g, stats=True)
-        again[first, count, g] = eng.trace_rhat(first, count, g, stats=True)
-  finally:
-    eng.close()
+  spec, x, res = big_run(name, _every_group_twice)
+  dev, again = ({(first, count, g): r[g][i] for (first, count), r in res.items() for g in GROUPS}
+                for i in range(2))
   return spec, x, dev, again
 
 
@@ -235,20 +223,8 @@ def test_refusals_leave_the_engine_working():
 
 
 def test_sampler_trace_rhat():
-  import probayes_amd as pb
-  from mcmc_examples import WORKLOADS
-  builder, params, _, _, _ = WORKLOADS['metrohast_norm1d']
-  g = oracle.load_golden('metrohast_norm1d')
-  params = oracle.workloads.golden_params(g) if params else params
-  process, init, extra, kwds, keys = builder(pb, params)
   n, t = 68, 96
-  sampler = process.sampler(init, extra, stop=t, chains=n, rng='philox', seed=7, **kwds)
-  try:
-    samples = process.walk(sampler)
-    assert len(samples) == t
-    v = process(samples).v
-    x = np.stack([np.asarray(v[k]).T for k in keys], axis=2)   # [n, t, d]
-    assert x.shape == (n, t, len(keys))
+  with sampler_block(n, t) as (sampler, process, x, keys, _):
     got = sampler.trace_rhat(8, 87, group=4)
     assert set(got) == {'split', 'nested'} and set(got['split']) == set(keys)
     host = diag.chain_moments(x, 8, 87)
@@ -265,5 +241,3 @@ def test_sampler_trace_rhat():
     process.next(sampler)
     with pytest.raises(ValueError, match='another block'):
       sampler.trace_rhat()
-  finally:
-    sampler.close()

@@ -15,9 +15,8 @@ import pytest
 import oracle
 from oracle.workloads import golden_init
 from probayes_amd import diag
-from test_gpu_pooled_quantile import Q64
 from test_gpu_quantile import _host_all
-from trace_helpers import run
+from trace_helpers import Q64, run
 
 pytestmark = pytest.mark.gpu
 

@@ -9,24 +9,17 @@ first block Q0 < NB, on the corners of the pair index and the chain id
 (seed, h, P, chain); its own reference is checked against the published
 known-answer vector."""
 import os
-import shutil
 import subprocess
 
 import pytest
+
+from host_program import compiler as _compiler
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'probayes_amd', 'csrc')
 DRAWS = 100000
 BLOCKS_PER_DRAW = 3 + 10 + 28        # sum over Q0 of NB - Q0, NB = 2, 4, 7
 CORNERS = 4 * 4 * 6 * 2
-
-
-def _compiler():
-  for name in ('c++', 'g++', 'clang++', '/opt/rocm/lib/llvm/bin/clang++'):
-    path = shutil.which(name)
-    if path:
-      return path
-  return None
 
 
 @pytest.fixture(scope='module')

@@ -9,25 +9,21 @@ possible half-integer rank at M = 4 096.
 
 And probayes_amd/csrc/pbh_rank_impl.h, the header the device kernels include,
 with pbh_trace_host.cpp's rank_layout, driven by the stand-alone program
-tests/rank_host_main.cpp built with a host compiler alone, -ffp-contract=off
+tests/trace_host_main.cpp built with a host compiler alone, -ffp-contract=off
 and the address and undefined-behaviour sanitizers, and run as a child
-process: its AS241 equals inv_cdf bit for bit everywhere (the same libm, the
+process (host_program.py): its AS241 equals inv_cdf bit for bit everywhere (the same libm, the
 same order), its run search equals np.searchsorted, and the refusal of M >=
 2^32 and the scratch geometry are right at the edges."""
-import os
-import shutil
 import statistics
-import subprocess
 
 import numpy as np
 import pytest
 
 from probayes_amd import diag
+from host_program import doubles, hex_words, host
 from rank_reference import ndtri, ref_rank_rhat, ref_ranks
 from rhat_reference import EPS, ar1_with_repeats, rel_dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'probayes_amd', 'csrc')
 M_SCORES = 4096
 INV = statistics.NormalDist().inv_cdf
 
@@ -152,51 +148,6 @@ def test_normal_scores_equal_inv_cdf():
 
 
 # ---- the header and the geometry, through the stand-alone program -----------
-def _compiler():
-  for name in ('c++', 'g++', 'clang++', '/opt/rocm/lib/llvm/bin/clang++'):
-    path = shutil.which(name)
-    if path:
-      return path
-  return None
-
-
-@pytest.fixture(scope='module')
-def host(tmp_path_factory):
-  """run(lines) -> the program's answers, one per request line"""
-  cxx = _compiler()
-  if cxx is None:
-    pytest.skip('no host C++ compiler')
-  tmp = tmp_path_factory.mktemp('rank_host')
-  exe = str(tmp / 'rank_host_main')
-  # the sanitizer runtimes linked into the program (clang's default), so that
-  # it runs whatever else the loader brings in first
-  version = subprocess.run([cxx, '--version'], capture_output=True, text=True).stdout
-  static = [] if 'clang' in version else ['-static-libasan', '-static-libubsan']
-  subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-Wall', '-ffp-contract=off',
-                         '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                        [os.path.join(ROOT, 'tests', 'rank_host_main.cpp'),
-                         os.path.join(CSRC, 'pbh_trace_host.cpp'), '-o', exe])
-
-  def run(lines):
-    req = tmp / 'requests.txt'
-    req.write_text(''.join(l + '\n' for l in lines))
-    r = subprocess.run([exe, str(req)], capture_output=True, text=True)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    out = r.stdout.splitlines()
-    assert len(out) == len(lines)
-    return out
-  return run
-
-
-def _hex(a):
-  return ' '.join('{:016x}'.format(int(b)) for b in
-                  np.ascontiguousarray(a, np.float64).reshape(-1).view(np.uint64))
-
-
-def _doubles(words):
-  return np.array([int(w, 16) for w in words], np.uint64).view(np.float64)
-
-
 def test_header_scores_equal_inv_cdf_bit_for_bit(host):
   r, p = _half_ranks()
   # the ends of (0, 1) and the two sides of each branch boundary: |q| = 0.425,
@@ -206,10 +157,10 @@ def test_header_scores_equal_inv_cdf_bit_for_bit(host):
           1. - np.exp(-25.), 0.5]
   p_all = np.concatenate([p, edge])
   want = np.array([INV(float(v)) for v in p_all])
-  got, scored = host(['ndtri ' + _hex(p_all), 'score {} {}'.format(M_SCORES, _hex(r))])
-  got = _doubles(got.split())
+  got, scored = host(['ndtri ' + hex_words(p_all), 'score {} {}'.format(M_SCORES, hex_words(r))])
+  got = doubles(got.split())
   assert got.tobytes() == want.tobytes(), np.flatnonzero(got != want)
-  assert _doubles(scored.split()).tobytes() == want[:r.size].tobytes()
+  assert doubles(scored.split()).tobytes() == want[:r.size].tobytes()
   # each branch was taken
   q = np.abs(p_all - 0.5)
   rr = np.sqrt(-np.log(np.minimum(p_all, 1. - p_all)))
@@ -242,7 +193,7 @@ def test_run_search_equals_searchsorted(host, name):
   hi = np.searchsorted(keys, keys, 'right')
   assert got.shape == (keys.size, 2)
   assert np.array_equal(got[:, 0], lo) and np.array_equal(got[:, 1], hi), name
-  assert np.array_equal(_doubles(ans[at + 1:]), (lo + hi + 1) / 2.)
+  assert np.array_equal(doubles(ans[at + 1:]), (lo + hi + 1) / 2.)
 
 
 def _layout(ans):
@@ -259,10 +210,11 @@ def test_layout_geometry_and_refusal(host):
   tile, most = 2048, 256
   sizes = [1, tile - 1, tile, tile + 1, most * tile, most * tile + 1, 2 * most * tile + 1,
            2**32 - 1]
-  lines = ['layout {} 1 3 100 1'.format(m) for m in sizes]
-  lines += ['layout {} 1 3 100 1'.format(2**32), 'layout 65536 65536 3 100 1',
-            'layout {} {} 1 0 0'.format(2**40, 2**40), 'layout 0 4 1 0 0', 'layout 4 0 1 0 0',
-            'layout 4 4 0 0 0', 'layout 2004 119 10 0 0', 'layout 65535 65537 2 7 1']
+  lines = ['rank_layout {} 1 3 100 1'.format(m) for m in sizes]
+  lines += ['rank_layout {} 1 3 100 1'.format(2**32), 'rank_layout 65536 65536 3 100 1',
+            'rank_layout {} {} 1 0 0'.format(2**40, 2**40), 'rank_layout 0 4 1 0 0',
+            'rank_layout 4 0 1 0 0', 'rank_layout 4 4 0 0 0', 'rank_layout 2004 119 10 0 0',
+            'rank_layout 65535 65537 2 7 1']
   ans = [_layout(a) for a in host(lines)]
   for m, l in zip(sizes, ans):
     assert l is not None and l['M'] == m

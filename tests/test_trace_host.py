@@ -8,25 +8,20 @@ The host arithmetic of the trace reductions: pbh_trace_host.cpp's window
 check, quantile-list check and pooled-quantile steps, driven by the
 stand-alone program tests/trace_host_main.cpp built with the address and
 undefined-behaviour sanitizers (and -ffp-contract=off, as the library builds
-the unit) and run as a child process.
+the unit) and run as a child process (host_program.py).
 
 The window check must give the verdict of first >= 0 and count >= min and
 first + count <= rec in unbounded integers for every corner of int64, with no
 overflow on the way (the sanitizer ends the program on one).  The pooled steps
 must place ranks and interpolate as diag.pooled_quantile does, bit for bit."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 from probayes_amd import diag
 from probayes_amd.engine import unpack_accept
-from test_gpu_pooled_quantile import Q64, QS
+from host_program import doubles, hex_words, host
+from trace_helpers import Q64, QS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'probayes_amd', 'csrc')
 I64_MIN, I64_MAX = -2**63, 2**63 - 1
 
 
@@ -45,51 +40,6 @@ def test_unpack_accept_equals_per_record_unpack(n, count):
   # chain c, record t is bit c % 64 of word c // 64
   t, c = count - 1, n - 1
   assert u[c, t] == (int(acc[t, c // 64]) >> (c % 64)) & 1
-
-
-def _compiler():
-  for name in ('c++', 'g++', 'clang++', '/opt/rocm/lib/llvm/bin/clang++'):
-    path = shutil.which(name)
-    if path:
-      return path
-  return None
-
-
-@pytest.fixture(scope='module')
-def host(tmp_path_factory):
-  """run(lines) -> the program's answers, one per request line"""
-  cxx = _compiler()
-  if cxx is None:
-    pytest.skip('no host C++ compiler')
-  tmp = tmp_path_factory.mktemp('trace_host')
-  exe = str(tmp / 'trace_host_main')
-  # the sanitizer runtimes linked into the program (clang's default), so that
-  # it runs whatever else the loader brings in first
-  version = subprocess.run([cxx, '--version'], capture_output=True, text=True).stdout
-  static = [] if 'clang' in version else ['-static-libasan', '-static-libubsan']
-  subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-Wall', '-ffp-contract=off',
-                         '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                        [os.path.join(ROOT, 'tests', 'trace_host_main.cpp'),
-                         os.path.join(CSRC, 'pbh_trace_host.cpp'), '-o', exe])
-
-  def run(lines):
-    req = tmp / 'requests.txt'
-    req.write_text(''.join(l + '\n' for l in lines))
-    r = subprocess.run([exe, str(req)], capture_output=True, text=True)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    out = r.stdout.splitlines()
-    assert len(out) == len(lines)
-    return out
-  return run
-
-
-def _hex(a):
-  return ' '.join('{:016x}'.format(int(b)) for b in
-                  np.ascontiguousarray(a, np.float64).reshape(-1).view(np.uint64))
-
-
-def _doubles(words):
-  return np.array([int(w, 16) for w in words], np.uint64).view(np.float64)
 
 
 def test_window_check_at_every_corner(host):
@@ -123,7 +73,7 @@ def _plan(m, q):
 
 @pytest.mark.parametrize('m', [1, 2, 3, 2004 * 119, 65536 * 1250, 2**40 + 1])
 def test_pooled_ranks(host, m):
-  for q, ans in zip((QS, Q64), host(['plan {} {} {}'.format(m, len(q), _hex(q))
+  for q, ans in zip((QS, Q64), host(['plan {} {} {}'.format(m, len(q), hex_words(q))
                                     for q in (QS, Q64)])):
     word = ans.split()
     at = word.index('ranks')
@@ -131,7 +81,7 @@ def test_pooled_ranks(host, m):
     lo, hi, g, targets = _plan(m, q)
     assert [int(w) for w in word[1:at:3]] == lo.tolist()
     assert [int(w) for w in word[2:at:3]] == hi.tolist()
-    assert _doubles(word[3:at:3]).tobytes() == g.tobytes()
+    assert doubles(word[3:at:3]).tobytes() == g.tobytes()
     ranks = [int(w) for w in word[at + 1:]]
     assert ranks == targets and ranks == sorted(set(ranks)) and m - 1 in ranks
 
@@ -158,13 +108,13 @@ def test_interpolation_equals_pooled_quantile(host, i):
   lines, wants = [], []
   for q in (QS, Q64, [.5]):
     lo, hi, _, targets = _plan(m, q)
-    lines.append('interp {} {} {} {} {}'.format(m, d, len(q), _hex(q), _hex(s[targets].T)))
+    lines.append('interp {} {} {} {} {}'.format(m, d, len(q), hex_words(q), hex_words(s[targets].T)))
     wants.append((diag.pooled_quantile(x, q), np.stack([s[lo], s[hi]], axis=1)))
   for (want, stats), ans in zip(wants, host(lines)):
     word = ans.split()
     at = word.index('stats')
-    assert _doubles(word[1:at]).tobytes() == want.tobytes(), (i, ans)
-    assert _doubles(word[at + 1:]).tobytes() == stats.tobytes(), i
+    assert doubles(word[1:at]).tobytes() == want.tobytes(), (i, ans)
+    assert doubles(word[at + 1:]).tobytes() == stats.tobytes(), i
   if i == 1:
     assert np.isnan(wants[0][0][:, 1]).all() and np.isfinite(wants[0][0][:, 0]).all()
   if i == 0:   # inf - inf between the two infinite neighbours
@@ -172,10 +122,10 @@ def test_interpolation_equals_pooled_quantile(host, i):
 
 
 def test_quantile_list_messages(host):
-  half = _hex([.5])
-  got = host(['qerr 0 1 ' + half, 'qerr 65 1 ' + half, 'qerr 2 2 ' + _hex([.5, -0.1]),
-              'qerr 1 1 ' + _hex([1.5]), 'qerr 3 3 ' + _hex([.25, .5, np.nan]),
-              'qerr 64 64 ' + _hex(Q64), 'qerr 10 10 ' + _hex(QS)])
+  half = hex_words([.5])
+  got = host(['qerr 0 1 ' + half, 'qerr 65 1 ' + half, 'qerr 2 2 ' + hex_words([.5, -0.1]),
+              'qerr 1 1 ' + hex_words([1.5]), 'qerr 3 3 ' + hex_words([.25, .5, np.nan]),
+              'qerr 64 64 ' + hex_words(Q64), 'qerr 10 10 ' + hex_words(QS)])
   assert got[0] == 'nq = 0 outside 1..64' and got[1] == 'nq = 65 outside 1..64'
   assert got[2] == 'q[1] = -0.1 is not a quantile in [0, 1]'
   assert got[3] == 'q[0] = 1.5 is not a quantile in [0, 1]'
