@@ -1,5 +1,7 @@
-// pbh_engine.hip -- the C-ABI of include/pbhip.h: engine state, device
-// memory, launches, HIP-event timing and the RCCL trace all-gather.
+// pbh_engine.hip -- the engine of include/pbhip.h's C-ABI: its state, device
+// memory (the resource cache), the resident server, launches, HIP-event
+// timing, checkpoints and the RCCL trace all-gather.  The trace entry points
+// are pbh_trace.cpp's, the ones that take no engine pbh_oneshot.cpp's.
 //
 // The engine owns every device buffer; the caller passes host pointers.
 // Nothing here throws across the C boundary: errors become status codes with
@@ -271,6 +273,14 @@ int srv_wait(pbh_engine *e, uint32_t seq, bool ok_if_ended) {
   }
 }
 
+// the command in flight (if any) has completed: one is in flight at a time
+int srv_settle(pbh_engine *e) {
+  if (!e->srv_pending) return PBH_OK;
+  const int rc = srv_wait(e, e->srv_pending, false);
+  e->srv_pending = 0;
+  return rc;
+}
+
 // a command where the server polls it: the host block (relay) or the device
 // mailbox through its host mapping (direct: stored through to the device)
 void srv_write(pbh_engine *e, uint32_t n, uint64_t arg, uint32_t q) {
@@ -388,11 +398,32 @@ int srv_launch(pbh_engine *e, pbh::KArgs k) {
   ++e->srv_launches;
   return PBH_OK;
 }
+
+// The wave-priority alternation of a launch (or command) of m steps: the
+// launch-relative clock at fair_short up to 64 steps (pbh_engine_state.h).
+struct Fair { int32_t fair, rel; };
+Fair launch_fair(const pbh_engine *e, int64_t m) {
+  return m <= 64 ? Fair{e->fair_short, 1} : Fair{e->fair, e->fair_rel};
+}
+
+// A running server may take a run of n_steps as a command: at most 2^30
+// steps, srv_arg's 48-bit step, and this run's own shape -- no moments, every step
+// recorded inside the trace, one pair-index high word.  The server's form
+// (model, proposal, RNG, trace) was checked at its launch, and every entry
+// point that changes it stops the server.
+bool srv_takes(const pbh_engine *e, int64_t n_steps) {
+  return n_steps <= (1 << 30) && e->g + n_steps < (int64_t(1) << 47) &&
+         !(e->collect & PBH_COLLECT_MOMENTS) && e->has_pred && e->cap > 0 && e->thin == 1 &&
+         e->g - e->rec_base >= 0 && e->g + n_steps - e->rec_base <= e->cap &&
+         pbh::pair_index_hi_const(e->g, n_steps);
+}
+
 // a run command (the previous one completed): n and arg, then seq
-void srv_submit(pbh_engine *e, int64_t n_steps, int32_t fair, int32_t fair_rel) {
+void srv_submit(pbh_engine *e, int64_t n_steps) {
   const uint32_t q = ++e->srv_seq;
+  const Fair f = launch_fair(e, n_steps);
   srv_write(e, (uint32_t)n_steps,
-            pbh::srv_arg(e->g, (uint32_t)fair, (uint32_t)fair_rel, pbh::kSrvRun, q), q);
+            pbh::srv_arg(e->g, (uint32_t)f.fair, (uint32_t)f.rel, pbh::kSrvRun, q), q);
   e->srv_pending = q;
   e->srv_last = srv_clk::now();
   e->g += n_steps;
@@ -403,16 +434,48 @@ void srv_submit(pbh_engine *e, int64_t n_steps, int32_t fair, int32_t fair_rel) 
   e->last_launches = 1;
   ++e->srv_commands;
 }
+
+// The timed region of a run's launches (pbh_last_run_ms): ev0 / ev1 as marker
+// packets around them, or (PBH_EVENT_MARKERS=0) on the first / last dispatch
+// packet through launch_events(), which every exit leaves cleared.
+class TimedRegion {
+  pbh_engine *e;
+  pbh::LaunchEvents &lev;
+
+ public:
+  explicit TimedRegion(pbh_engine *eng) : e(eng), lev(pbh::launch_events()) {}
+  ~TimedRegion() { lev = {}; }
+  int open() {
+    e->srv_timed = false;
+    if (e->event_markers) HIP_TRY(hipEventRecord(e->ev0, e->stream));
+    lev = {e->event_markers ? nullptr : e->ev0, nullptr};
+    return PBH_OK;
+  }
+  // before the run's last dispatch
+  void last_dispatch() {
+    if (!e->event_markers) lev.stop = e->ev1;
+  }
+  int close() {
+    lev = {};
+    if (e->event_markers) HIP_TRY(hipEventRecord(e->ev1, e->stream));
+    return PBH_OK;
+  }
+};
+
+// what a run leaves for pbh_get_moments and pbh_last_run_ms; a run of no
+// steps has launched and timed nothing
+int run_closed(pbh_engine *e, int64_t n_steps, int64_t launches) {
+  e->mom_steps += n_steps;
+  e->timed = n_steps > 0;
+  e->last_launches = launches;
+  return PBH_OK;
+}
 }  // namespace
 
 int pbh::srv_stop(pbh_engine *e) {
   if (!e->srv_active) return PBH_OK;
   HIP_TRY(hipSetDevice(e->device));
-  int rc = PBH_OK;
-  if (e->srv_pending) {
-    rc = srv_wait(e, e->srv_pending, false);
-    e->srv_pending = 0;
-  }
+  int rc = srv_settle(e);
   if (!srv_kernel_ended(e)) {
     const uint32_t q = ++e->srv_seq;
     srv_write(e, 0u, pbh::srv_arg(0, 0u, 0u, pbh::kSrvExit, q), q);
@@ -427,7 +490,6 @@ int pbh::srv_stop(pbh_engine *e) {
 }
 
 extern "C" {
-
 
 const char *pbh_last_error(void) { return g_err.c_str(); }
 
@@ -602,13 +664,6 @@ int pbh_cache_info(int64_t *idle_bytes, int64_t *hits, int64_t *misses) {
 // ---------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------
-// PBH_EXPR_DATA_WIDE=0: the bodies one observation at a time (the comparison
-// form; the default decodes a body word once per block of 8 observations)
-static int32_t expr_data_wide() {
-  const char *v = std::getenv("PBH_EXPR_DATA_WIDE");
-  return (v && v[0] == '0') ? 0 : 1;
-}
-
 int pbh_set_model(pbh_engine *e, const pbh_model *m) {
   if (check_ptr(e, "engine") || check_ptr(m, "model")) return PBH_ERR_ARG;
   SRV_STOP(e);
@@ -742,7 +797,7 @@ int pbh_set_model(pbh_engine *e, const pbh_model *m) {
   k.ta = base + oa; k.tb = base + ob; k.tc = base + oc; k.te = base + oe;
   k.tw = base + ow; k.ksum = ksum;
   pbh::expr_bind(k, base, lay);
-  k.ewide = expr_data_wide();
+  k.ewide = pbh::expr_data_wide();
   k.tn = (m->target_kind == PBH_TARGET_NORM_IID || m->target_kind == PBH_TARGET_GMM) ? m->n : 0;
   k.i0 = m->i0; k.i1 = m->i1;
   k.has_prior = m->has_prior ? 1 : 0;
@@ -1185,13 +1240,19 @@ static int32_t ahead_want(const pbh::LegacyArgs &a, int64_t m) {
   return std::min<int32_t>(15, 1 + (int32_t)std::ceil(ahead_words(a, m) / pbh_mt_block_words()));
 }
 
-int pbh_legacy_replay(pbh_engine *e, int64_t n_steps) {
-  if (check_ptr(e, "engine")) return PBH_ERR_ARG;
-  SRV_STOP(e);
+// the legacy streams may draw: seeded, and not left behind by a pbh_restore
+static int legacy_ready(const pbh_engine *e) {
   if (!e->mt_key) return fail(PBH_ERR_STATE, "pbh_legacy_seed first");
   if (e->mt_stale)
     return fail(PBH_ERR_STATE, "pbh_restore ran after pbh_legacy_seed: set the "
                 "checkpoint's legacy state (pbh_set_legacy_state) first");
+  return PBH_OK;
+}
+
+int pbh_legacy_replay(pbh_engine *e, int64_t n_steps) {
+  if (check_ptr(e, "engine")) return PBH_ERR_ARG;
+  SRV_STOP(e);
+  if (const int rc = legacy_ready(e)) return rc;
   int32_t R = 0;
   int rc = pbh_stream_width(e, &R);
   if (rc) return rc;
@@ -1449,11 +1510,7 @@ int pbh_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
                    std::chrono::duration<double, std::micro>(clk::now() - tq0).count());
   };
   if (const int rc = run_checks(e, n_steps)) return rc;
-  if (n_steps == 0) {
-    e->timed = false;
-    e->last_launches = 0;
-    return PBH_OK;
-  }
+  if (n_steps == 0) return run_closed(e, 0, 0);
   if (e->rng == PBH_RNG_REPLAY &&
       (!e->rep || e->g < e->rep_g0 || e->g + n_steps > e->rep_g0 + e->rep_steps))
     return fail(PBH_ERR_STATE,
@@ -1464,19 +1521,10 @@ int pbh_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
   // kernel-argument block, no device call; the server's form was checked at
   // its launch and every entry point that could change it stops it)
   if (e->srv_active && (steps_per_launch <= 0 || steps_per_launch >= n_steps) &&
-      n_steps <= (1 << 30) && e->g + n_steps < (int64_t(1) << 47) &&
-      !(e->collect & PBH_COLLECT_MOMENTS) && e->has_pred && e->cap > 0 && e->thin == 1 &&
-      e->g - e->rec_base >= 0 && e->g + n_steps - e->rec_base <= e->cap &&
-      pbh::pair_index_hi_const(e->g, n_steps)) {
-    if (e->srv_pending) {
-      const int rc = srv_wait(e, e->srv_pending, false);
-      e->srv_pending = 0;
-      if (rc) return rc;
-    }
+      srv_takes(e, n_steps)) {
+    if (const int rc = srv_settle(e)) return rc;
     if (srv_clk::now() - e->srv_last <= std::chrono::milliseconds(e->srv_idle_ms / 2)) {
-      const bool short_run = n_steps <= 64;
-      srv_submit(e, n_steps, short_run ? e->fair_short : e->fair,
-                 short_run ? 1 : e->fair_rel);
+      srv_submit(e, n_steps);
       tq("server command (fast path)");
       return PBH_OK;
     }
@@ -1499,27 +1547,19 @@ int pbh_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
     kc.g0 = e->g;
     kc.n_steps = (int32_t)n_steps;
     kc.has_pred = e->has_pred ? 1 : 0;
-    const bool short_run = n_steps <= 64;
-    kc.fair = short_run ? e->fair_short : e->fair;
-    kc.fair_rel = short_run ? 1 : e->fair_rel;
+    const Fair f = launch_fair(e, n_steps);
+    kc.fair = f.fair; kc.fair_rel = f.rel;
     kc.srv_cmd = kc.srv_done = kc.srv_mail = reinterpret_cast<void *>(1);   // the check only
     int32_t wgs = 0;
-    // a running server's form (model, proposal, RNG, trace) was checked at
-    // its launch -- every entry point that changes them stops it -- so only
-    // this run's own shape is checked (no occupancy query per command)
-    const bool form = e->g + n_steps < (int64_t(1) << 47) &&   // srv_arg's 48-bit step
-        (e->srv_active
-             ? (!k.moments && e->has_pred && e->cap > 0 && e->thin == 1 &&
-                e->g - e->rec_base >= 0 && e->g + n_steps - e->rec_base <= e->cap &&
-                pbh::pair_index_hi_const(e->g, n_steps))
-             : pbh::launch_mh_server(kc, e->stream, &wgs, true) == hipSuccess);
+    // a running server: only this run's own shape is checked (no occupancy
+    // query per command)
+    const bool form =
+        e->srv_active ? srv_takes(e, n_steps)
+                      : e->g + n_steps < (int64_t(1) << 47) &&   // srv_arg's 48-bit step
+                            pbh::launch_mh_server(kc, e->stream, &wgs, true) == hipSuccess;
     if (form) {
       if (e->srv_active) {
-        if (e->srv_pending) {   // one command in flight
-          const int rc = srv_wait(e, e->srv_pending, false);
-          e->srv_pending = 0;
-          if (rc) return rc;
-        }
+        if (const int rc = srv_settle(e)) return rc;
         // a server that has ended, or whose idle exit could be near, is
         // replaced: a command never races the kernel's own exit
         const auto idle = srv_clk::now() - e->srv_last;
@@ -1535,34 +1575,24 @@ int pbh_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
         const int rc = srv_launch(e, kc);
         if (rc) return rc;
       }
-      srv_submit(e, n_steps, kc.fair, kc.fair_rel);
+      srv_submit(e, n_steps);
       tq("server command");
       return PBH_OK;
     }
     (void)hipGetLastError();
   }
   SRV_STOP(e);
-  e->srv_timed = false;
-  // the timed region: events on the first / last dispatch packet, or (with
-  // PBH_EVENT_MARKERS=1) separate marker packets around the launches
-  pbh::LaunchEvents &lev = pbh::launch_events();
   tq("args");
-  if (e->event_markers) {
-    HIP_TRY(hipEventRecord(e->ev0, e->stream));
-    tq("event0");
-    lev = {};
-  } else {
-    lev.start = e->ev0;
-    lev.stop = nullptr;
-  }
+  TimedRegion timed(e);
+  if (const int rc = timed.open()) return rc;
+  if (e->event_markers) tq("event0");
   int64_t launches = 0;
   for (int64_t done = 0; done < n_steps;) {
     const int64_t m = std::min(spl, n_steps - done);
-    if (!e->event_markers && done + m >= n_steps) lev.stop = e->ev1;
+    if (done + m >= n_steps) timed.last_dispatch();
     k.n_steps = (int32_t)m;
-    const bool short_launch = m <= 64;
-    k.fair = short_launch ? e->fair_short : e->fair;
-    k.fair_rel = short_launch ? 1 : e->fair_rel;
+    const Fair f = launch_fair(e, m);
+    k.fair = f.fair; k.fair_rel = f.rel;
     k.g0 = e->g;
     k.has_pred = e->has_pred ? 1 : 0;
     k.rep_row0 = e->g - e->rep_g0;
@@ -1571,10 +1601,8 @@ int pbh_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
     k.lx_init = e->lx_valid ? 0 : 1;
     hipError_t err = e->has_gibbs ? pbh::launch_gibbs(k, e->stream)
                                   : pbh::launch_mh(k, e->stream, lds);
-    if (err != hipSuccess) {
-      lev = {};
+    if (err != hipSuccess)
       return fail(PBH_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(err));
-    }
     e->g += m;
     e->has_pred = true;
     e->gq_valid = gfast;   // only the production Gibbs kernel maintains g, Q
@@ -1584,14 +1612,10 @@ int pbh_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
     done += m;
     ++launches;
   }
-  lev = {};
   tq("launches");
-  if (e->event_markers) HIP_TRY(hipEventRecord(e->ev1, e->stream));
+  if (const int rc = timed.close()) return rc;
   tq("event1");
-  e->mom_steps += n_steps;
-  e->timed = true;
-  e->last_launches = launches;
-  return PBH_OK;
+  return run_closed(e, n_steps, launches);
 }
 
 // Generation and the REPLAY chain-step in one kernel per launch (pbh_legacy.hip
@@ -1606,16 +1630,9 @@ int pbh_legacy_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
   SRV_STOP(e);
   if (e->rng != PBH_RNG_REPLAY)
     return fail(PBH_ERR_STATE, "pbh_legacy_run runs the REPLAY RNG (pbh_set_rng)");
-  if (!e->mt_key) return fail(PBH_ERR_STATE, "pbh_legacy_seed first");
-  if (e->mt_stale)
-    return fail(PBH_ERR_STATE, "pbh_restore ran after pbh_legacy_seed: set the "
-                "checkpoint's legacy state (pbh_set_legacy_state) first");
+  if (const int rc = legacy_ready(e)) return rc;
   if (const int rc = run_checks(e, n_steps)) return rc;
-  if (n_steps == 0) {
-    e->timed = false;
-    e->last_launches = 0;
-    return PBH_OK;
-  }
+  if (n_steps == 0) return run_closed(e, 0, 0);
   const int64_t spl = steps_per_launch > 0 ? steps_per_launch : n_steps;
   int32_t R = 0;
   if (const int rc = pbh_stream_width(e, &R)) return rc;
@@ -1656,15 +1673,8 @@ int pbh_legacy_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
     e->thr_steps = keep_thr ? n_steps : 0;
     return PBH_OK;
   }
-  e->srv_timed = false;
-  pbh::LaunchEvents &lev = pbh::launch_events();
-  if (e->event_markers) {
-    HIP_TRY(hipEventRecord(e->ev0, e->stream));
-    lev = {};
-  } else {
-    lev.start = e->ev0;
-    lev.stop = nullptr;
-  }
+  TimedRegion timed(e);
+  if (const int rc = timed.open()) return rc;
   // the twist-ahead pass: the fused kernel then only consumes
   const bool ahead = e->legacy_ahead && e->mt_k4 && !e->mt_odd;
   const int64_t m_fit = ahead ? ahead_fit(la, spl) : spl;
@@ -1674,12 +1684,10 @@ int pbh_legacy_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
     if (ahead) {
       const hipError_t ea = pbh::launch_legacy_ahead(e->mt_key, e->mt_pos, e->n,
                                                      ahead_want(la, m), e->stream);
-      if (ea != hipSuccess) {
-        lev = {};
+      if (ea != hipSuccess)
         return fail(PBH_ERR_HIP, "pbh_legacy_run (twist-ahead): %s", hipGetErrorString(ea));
-      }
     }
-    if (!e->event_markers && done + m >= n_steps) lev.stop = e->ev1;
+    if (done + m >= n_steps) timed.last_dispatch();
     k.n_steps = (int32_t)m;
     k.g0 = e->g;
     k.has_pred = e->has_pred ? 1 : 0;
@@ -1690,17 +1698,14 @@ int pbh_legacy_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
     la.step0 = e->g;
     la.thr = keep_thr ? e->thr + (size_t)done * e->n : nullptr;
     const hipError_t err = pbh::launch_legacy_mh(la, k, e->stream, false);
-    if (err != hipSuccess) {
-      lev = {};
+    if (err != hipSuccess)
       return fail(PBH_ERR_HIP, "pbh_legacy_run: %s", hipGetErrorString(err));
-    }
     e->g += m;
     e->has_pred = true;
     done += m;
     ++launches;
   }
-  lev = {};
-  if (e->event_markers) HIP_TRY(hipEventRecord(e->ev1, e->stream));
+  if (const int rc = timed.close()) return rc;
   e->gq_valid = false;
   e->lx_valid = false;
   e->thr_steps = keep_thr ? n_steps : 0;
@@ -1708,10 +1713,7 @@ int pbh_legacy_run(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
   e->k.R = R;
   e->rep_steps = 0;
   e->rep_g0 = e->g;
-  e->mom_steps += n_steps;
-  e->timed = true;
-  e->last_launches = launches;
-  return PBH_OK;
+  return run_closed(e, n_steps, launches);
 }
 
 int pbh_run_wait(pbh_engine *e, int64_t n_steps, int32_t steps_per_launch) {
@@ -1744,10 +1746,7 @@ int pbh_legacy_draws(pbh_engine *e, int64_t n_steps, int64_t step0, int32_t kind
                      double param, double *out) {
   if (check_ptr(e, "engine") || check_ptr(out, "out")) return PBH_ERR_ARG;
   SRV_STOP(e);
-  if (!e->mt_key) return fail(PBH_ERR_STATE, "pbh_legacy_seed first");
-  if (e->mt_stale)
-    return fail(PBH_ERR_STATE, "pbh_restore ran after pbh_legacy_seed: set the "
-                "checkpoint's legacy state (pbh_set_legacy_state) first");
+  if (const int rc = legacy_ready(e)) return rc;
   if (!e->mt_k4) return fail(PBH_ERR_UNSUPPORTED, "pbh_legacy_draws needs the Mt4 state");
   if (kind != PBH_DRAWS_GAUSS && kind != PBH_DRAWS_LINREG)
     return fail(PBH_ERR_ARG, "bad draws kind %d", kind);
@@ -1774,14 +1773,7 @@ int pbh_legacy_draws(pbh_engine *e, int64_t n_steps, int64_t step0, int32_t kind
 
 int pbh_sync(pbh_engine *e) {
   if (check_ptr(e, "engine")) return PBH_ERR_ARG;
-  if (e->srv_active) {   // never the stream: the server kernel is on it
-    if (e->srv_pending) {
-      const int rc = srv_wait(e, e->srv_pending, false);
-      e->srv_pending = 0;
-      return rc;
-    }
-    return PBH_OK;
-  }
+  if (e->srv_active) return srv_settle(e);   // never the stream: the server kernel is on it
   HIP_TRY(hipSetDevice(e->device));
   if (e->spin_sync) {
     // poll the stream for up to 2 ms: a short launch's completion is seen
@@ -1888,8 +1880,7 @@ int pbh_get_state(pbh_engine *e, double *x, double *logp) {
   if (x) {
     std::vector<double> xt((size_t)n * d);
     HIP_TRY(hipMemcpy(xt.data(), e->x, xt.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int64_t c = 0; c < n; ++c)
-      for (int k = 0; k < d; ++k) x[(size_t)c * d + k] = xt[(size_t)k * n + c];
+    pbh::dim_major_to_rows(xt.data(), x, n, d);
   }
   if (logp) HIP_TRY(hipMemcpy(logp, e->lp, n * sizeof(double), hipMemcpyDeviceToHost));
   return PBH_OK;
@@ -1916,22 +1907,22 @@ int pbh_get_checkpoint(pbh_engine *e, double *x, double *lp, int64_t *step,
   return PBH_OK;
 }
 
-int pbh_restore(pbh_engine *e, const double *x, const double *lp, int64_t step,
-                int32_t has_pred, const uint32_t *xo) {
+// pbh_set_chains, and with `restore` pbh_restore: the same replacement of the
+// chain state, plus the xoshiro state xo and seeded legacy streams gone stale.
+static int replace_chains(pbh_engine *e, const double *x, const double *lp, int64_t step,
+                          int32_t has_pred, bool restore, const uint32_t *xo) {
   if (check_ptr(e, "engine") || check_ptr(x, "x") || check_ptr(lp, "lp"))
     return PBH_ERR_ARG;
   SRV_STOP(e);
   if (!e->x) return fail(PBH_ERR_STATE, "pbh_init_chains first");
   if (step < 0) return fail(PBH_ERR_ARG, "step index must be >= 0");
-  if (e->rng == PBH_RNG_XOSHIRO && !xo)
+  if (restore && e->rng == PBH_RNG_XOSHIRO && !xo)
     return fail(PBH_ERR_ARG, "XOSHIRO needs the generator state xo");
   const int64_t n = e->n;
-  const int d = e->d;
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  std::vector<double> xt((size_t)n * d);
-  for (int64_t c = 0; c < n; ++c)
-    for (int k = 0; k < d; ++k) xt[(size_t)k * n + c] = x[(size_t)c * d + k];
+  std::vector<double> xt((size_t)n * e->d);
+  pbh::rows_to_dim_major(x, xt.data(), n, e->d);
   HIP_TRY(hipMemcpy(e->x, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->lp, lp, n * sizeof(double), hipMemcpyHostToDevice));
   if (xo) {
@@ -1945,40 +1936,23 @@ int pbh_restore(pbh_engine *e, const double *x, const double *lp, int64_t step,
   e->gq_valid = false;   // the production Gibbs kernel recomputes g, Q from x
   e->state_lost = false;
   e->lx_valid = false;   // ... and the ufun logs (pbh_set_chain_logs restores them)
-  e->cap = 0;            // a trace / replay rows of the engine are detached
+  e->cap = 0;            // the trace and the replay rows are detached
   e->rep_steps = 0;
   e->rep_g0 = step;
   // device legacy streams: their state is not in x / lp / step; until the
   // checkpoint's is set (pbh_set_legacy_state) the streams refuse to draw
-  e->mt_stale = e->mt_key != nullptr;
+  if (restore) e->mt_stale = e->mt_key != nullptr;
   return PBH_OK;
+}
+
+int pbh_restore(pbh_engine *e, const double *x, const double *lp, int64_t step,
+                int32_t has_pred, const uint32_t *xo) {
+  return replace_chains(e, x, lp, step, has_pred, true, xo);
 }
 
 int pbh_set_chains(pbh_engine *e, const double *x, const double *lp,
                    int64_t step, int32_t has_pred) {
-  if (check_ptr(e, "engine") || check_ptr(x, "x") || check_ptr(lp, "lp"))
-    return PBH_ERR_ARG;
-  SRV_STOP(e);
-  if (!e->x) return fail(PBH_ERR_STATE, "pbh_init_chains first");
-  if (step < 0) return fail(PBH_ERR_ARG, "step index must be >= 0");
-  const int64_t n = e->n;
-  const int d = e->d;
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  std::vector<double> xt((size_t)n * d);
-  for (int64_t c = 0; c < n; ++c)
-    for (int k = 0; k < d; ++k) xt[(size_t)k * n + c] = x[(size_t)c * d + k];
-  HIP_TRY(hipMemcpy(e->x, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->lp, lp, n * sizeof(double), hipMemcpyHostToDevice));
-  e->g = step;
-  e->has_pred = has_pred != 0;
-  e->gq_valid = false;
-  e->lx_valid = false;
-  e->cap = 0;            // the trace and the replay rows are detached
-  e->state_lost = false;
-  e->rep_steps = 0;
-  e->rep_g0 = step;
-  return PBH_OK;
+  return replace_chains(e, x, lp, step, has_pred, false, nullptr);
 }
 
 int pbh_get_chain_logs(pbh_engine *e, double *lx, int32_t *valid) {
@@ -1992,8 +1966,7 @@ int pbh_get_chain_logs(pbh_engine *e, double *lx, int32_t *valid) {
   const int64_t n = e->n, d = e->d;
   std::vector<double> t((size_t)n * d);
   HIP_TRY(hipMemcpy(t.data(), e->lx, t.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (int64_t c = 0; c < n; ++c)
-    for (int64_t k = 0; k < d; ++k) lx[(size_t)c * d + k] = t[(size_t)k * n + c];
+  pbh::dim_major_to_rows(t.data(), lx, n, d);
   return PBH_OK;
 }
 
@@ -2005,8 +1978,7 @@ int pbh_set_chain_logs(pbh_engine *e, const double *lx) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   const int64_t n = e->n, d = e->d;
   std::vector<double> t((size_t)n * d);
-  for (int64_t c = 0; c < n; ++c)
-    for (int64_t k = 0; k < d; ++k) t[(size_t)k * n + c] = lx[(size_t)c * d + k];
+  pbh::rows_to_dim_major(lx, t.data(), n, d);
   HIP_TRY(hipMemcpy(e->lx, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
   e->lx_valid = true;
   return PBH_OK;
@@ -2286,371 +2258,6 @@ int pbh_rccl_destroy(pbh_engine *e) {
     RCCL_TRY(ncclCommDestroy(e->comm));
     e->comm = nullptr;
   }
-  return PBH_OK;
-}
-
-int pbh_check_accept(int device, int64_t n, const double *lp,
-                     const double *lpp, const uint32_t *t0, const uint32_t *t1,
-                     int32_t lin, uint8_t *out) {
-  if (check_ptr(lp, "lp") || check_ptr(lpp, "lpp") || check_ptr(t0, "t0") ||
-      check_ptr(t1, "t1") || check_ptr(out, "out"))
-    return PBH_ERR_ARG;
-  if (n <= 0) return fail(PBH_ERR_ARG, "n must be positive");
-  HIP_TRY(hipSetDevice(device));
-  double *dlp = nullptr, *dlpp = nullptr;
-  uint32_t *d0 = nullptr, *d1 = nullptr;
-  uint8_t *dout = nullptr;
-  int rc = dalloc(dlp, n);
-  if (!rc) rc = dalloc(dlpp, n);
-  if (!rc) rc = dalloc(d0, n);
-  if (!rc) rc = dalloc(d1, n);
-  if (!rc) rc = dalloc(dout, n);
-  hipError_t err = hipSuccess;
-  if (!rc) {
-    err = hipMemcpy(dlp, lp, n * sizeof(double), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(dlpp, lpp, n * sizeof(double), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(d0, t0, n * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(d1, t1, n * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess)
-      err = pbh::launch_check_accept(n, dlp, dlpp, d0, d1, lin,
-                                     std::log(1.7976931348623158e+308), dout);
-    if (err == hipSuccess) err = hipMemcpy(out, dout, n, hipMemcpyDeviceToHost);
-  }
-  dfree(dlp); dfree(dlpp); dfree(d0); dfree(d1); dfree(dout);
-  if (rc) return rc;
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_check_accept: %s", hipGetErrorString(err));
-  return PBH_OK;
-}
-
-static int eval_expr_impl(const char *fn, int device, const pbh::ExprProgram &p, int64_t n,
-                          const double *x, double *out) {
-  if (check_ptr(x, "x") || check_ptr(out, "out")) return PBH_ERR_ARG;
-  if (n <= 0) return fail(PBH_ERR_ARG, "n must be positive");
-  int pc = -1;
-  if (const char *why = pbh::expr_check(p, &pc))
-    return fail(PBH_ERR_ARG, "expression program: %s (code word %d)", why, pc);
-  HIP_TRY(hipSetDevice(device));
-  std::vector<double> blk;
-  const pbh::ExprLayout lay = pbh::expr_pack(blk, p);
-  const int32_t d = p.d;
-  std::vector<double> xt((size_t)d * n);   // [n][d] -> [d][n]
-  for (int64_t i = 0; i < n; ++i)
-    for (int k = 0; k < d; ++k) xt[(size_t)k * n + i] = x[(size_t)i * d + k];
-  double *dblk = nullptr, *dx = nullptr, *dout = nullptr;
-  int rc = dalloc(dblk, blk.size());
-  if (!rc) rc = dalloc(dx, xt.size());
-  if (!rc) rc = dalloc(dout, n);
-  hipError_t err = hipSuccess;
-  if (!rc) {
-    err = hipMemcpy(dblk, blk.data(), blk.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (err == hipSuccess)
-      err = hipMemcpy(dx, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
-      KArgs k{};
-      k.d = d;
-      k.target = PBH_TARGET_EXPR;
-      pbh::expr_bind(k, dblk, lay);
-      k.ewide = expr_data_wide();
-      err = pbh::launch_eval_expr(k, n, dx, dout);
-    }
-    if (err == hipSuccess) err = hipMemcpy(out, dout, n * sizeof(double), hipMemcpyDeviceToHost);
-  }
-  dfree(dblk); dfree(dx); dfree(dout);
-  if (rc) return rc;
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "%s: %s", fn, hipGetErrorString(err));
-  return PBH_OK;
-}
-
-int pbh_eval_expr(int device, int32_t d, const int32_t *code, int32_t n_code,
-                  const double *consts, int32_t n_consts, int32_t depth, int64_t n,
-                  const double *x, double *out) {
-  return eval_expr_impl("pbh_eval_expr", device,
-                        {d, code, n_code, consts, n_consts, depth, nullptr, 0, 0}, n, x, out);
-}
-
-int pbh_eval_expr_data(int device, int32_t d, const int32_t *code, int32_t n_code,
-                       const double *consts, int32_t n_consts, int32_t depth,
-                       const double *data, int32_t n_cols, int32_t n_obs, int64_t n,
-                       const double *x, double *out) {
-  if (check_ptr(data, "data")) return PBH_ERR_ARG;
-  return eval_expr_impl("pbh_eval_expr_data", device,
-                        {d, code, n_code, consts, n_consts, depth, data, n_cols, n_obs}, n, x,
-                        out);
-}
-
-int pbh_bool_perm_freq(int device, int64_t rows, int32_t cols,
-                       const uint8_t *bool2d, int64_t *counts, int32_t reps,
-                       double *kernel_ms) {
-  if (check_ptr(counts, "counts")) return PBH_ERR_ARG;
-  if (cols < 1 || cols > pbh::bool_perm_max_cols())
-    return fail(PBH_ERR_ARG, "cols must be in 1..%d, got %d",
-                pbh::bool_perm_max_cols(), cols);
-  if (rows < 0) return fail(PBH_ERR_ARG, "rows must be >= 0");
-  if (rows > 0 && !bool2d) return fail(PBH_ERR_ARG, "bool2d must not be NULL");
-  if (reps < 1) return fail(PBH_ERR_ARG, "reps must be >= 1");
-  const int64_t nbins = (int64_t)1 << cols;
-  if (kernel_ms) *kernel_ms = 0.;
-  if (rows == 0) {
-    std::memset(counts, 0, nbins * sizeof(int64_t));
-    return PBH_OK;
-  }
-  HIP_TRY(hipSetDevice(device));
-  int n_cu = 0;
-  HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
-  uint8_t *din = nullptr;
-  unsigned long long *dcnt = nullptr, *dscr = nullptr;
-  int rc = dalloc(din, rows * cols);
-  if (!rc) rc = dalloc(dcnt, nbins);
-  if (!rc) rc = dalloc(dscr, pbh::bool_perm_scratch_words(n_cu));
-  hipError_t err = hipSuccess;
-  hipStream_t st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  double total = 0.;
-  if (!rc) {
-    err = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipEventCreate(&e0);
-    if (err == hipSuccess) err = hipEventCreate(&e1);
-    if (err == hipSuccess)
-      err = hipMemcpy(din, bool2d, (size_t)(rows * cols), hipMemcpyHostToDevice);
-    // r = 0 is an untimed warm-up launch (the code object loads lazily on
-    // the first launch); the average is over the `reps` timed launches
-    for (int r = 0; r <= reps && err == hipSuccess; ++r) {
-      err = hipMemsetAsync(dcnt, 0, nbins * sizeof(unsigned long long), st);
-      if (err == hipSuccess) err = hipEventRecord(e0, st);
-      if (err == hipSuccess) err = pbh::launch_bool_perm_freq(din, rows, cols, dcnt, dscr, n_cu, st);
-      if (err == hipSuccess) err = hipEventRecord(e1, st);
-      if (err == hipSuccess) err = hipEventSynchronize(e1);
-      float ms = 0.f;
-      if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
-      if (r > 0) total += ms;
-    }
-    if (err == hipSuccess)
-      err = hipMemcpy(counts, dcnt, nbins * sizeof(int64_t), hipMemcpyDeviceToHost);
-  }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  dfree(din); dfree(dcnt); dfree(dscr);
-  if (rc) return rc;
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_bool_perm_freq: %s", hipGetErrorString(err));
-  if (kernel_ms) *kernel_ms = total / reps;
-  return PBH_OK;
-}
-
-int pbh_check_normals64(int device, int64_t n, const uint32_t *words,
-                        double *fast, double *ref) {
-  if (check_ptr(words, "words") || check_ptr(fast, "fast") || check_ptr(ref, "ref"))
-    return PBH_ERR_ARG;
-  if (n <= 0) return fail(PBH_ERR_ARG, "n must be positive");
-  HIP_TRY(hipSetDevice(device));
-  std::vector<double> tab(pbh::kBm64Doubles);
-  pbh::bm64_tables(tab.data());
-  uint32_t *dw = nullptr;
-  double *df = nullptr, *dr = nullptr, *dt = nullptr;
-  int rc = dalloc(dw, 3 * n);
-  if (!rc) rc = dalloc(df, 2 * n);
-  if (!rc) rc = dalloc(dr, 2 * n);
-  if (!rc) rc = dalloc(dt, tab.size());
-  hipError_t err = hipSuccess;
-  if (!rc) {
-    err = hipMemcpy(dw, words, 3 * n * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess)
-      err = hipMemcpy(dt, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = pbh::launch_check_normals64(n, dw, dt, df, dr);
-    if (err == hipSuccess) err = hipMemcpy(fast, df, 2 * n * sizeof(double), hipMemcpyDeviceToHost);
-    if (err == hipSuccess) err = hipMemcpy(ref, dr, 2 * n * sizeof(double), hipMemcpyDeviceToHost);
-  }
-  dfree(dw); dfree(df); dfree(dr); dfree(dt);
-  if (rc) return rc;
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_check_normals64: %s", hipGetErrorString(err));
-  return PBH_OK;
-}
-
-int pbh_bm64_tables(double *out) {
-  if (check_ptr(out, "out")) return PBH_ERR_ARG;
-  pbh::bm64_tables(out);
-  return PBH_OK;
-}
-
-int pbh_check_normals(int device, int64_t n, const uint32_t *words,
-                      double *fast, double *ref) {
-  if (check_ptr(words, "words") || check_ptr(fast, "fast") || check_ptr(ref, "ref"))
-    return PBH_ERR_ARG;
-  if (n <= 0) return fail(PBH_ERR_ARG, "n must be positive");
-  HIP_TRY(hipSetDevice(device));
-  uint32_t *dw = nullptr;
-  double *df = nullptr, *dr = nullptr;
-  int rc = dalloc(dw, 4 * n);
-  if (!rc) rc = dalloc(df, 2 * n);
-  if (!rc) rc = dalloc(dr, 2 * n);
-  hipError_t err = hipSuccess;
-  if (!rc) {
-    err = hipMemcpy(dw, words, 4 * n * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = pbh::launch_check_normals(n, dw, df, dr);
-    if (err == hipSuccess) err = hipMemcpy(fast, df, 2 * n * sizeof(double), hipMemcpyDeviceToHost);
-    if (err == hipSuccess) err = hipMemcpy(ref, dr, 2 * n * sizeof(double), hipMemcpyDeviceToHost);
-  }
-  dfree(dw); dfree(df); dfree(dr);
-  if (rc) return rc;
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_check_normals: %s", hipGetErrorString(err));
-  return PBH_OK;
-}
-
-
-// numpy's pairwise sum of a contiguous float64 array (the 8-accumulator
-// leaf of <= 128 terms, split at n/2 rounded down to a multiple of 8).
-static double np_pairwise_host(const double *a, int64_t n) {
-  if (n < 8) {
-    double r = 0.;
-    for (int64_t i = 0; i < n; ++i) r += a[i];
-    return r;
-  }
-  if (n <= 128) {
-    double r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int64_t i = 8;
-    for (; i < n - (n % 8); i += 8)
-      for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-  }
-  int64_t n2 = n / 2;
-  n2 -= n2 % 8;
-  return np_pairwise_host(a, n2) + np_pairwise_host(a + n2, n - n2);
-}
-
-int pbh_linreg_gibbs(int device, int64_t n_obs, const double *x_obs,
-                     const double *y_obs, const double *hyper,
-                     const double *vsets, int64_t n_chains,
-                     int64_t chain_offset, int64_t n_steps, int64_t step0,
-                     const double *init, int32_t rng_mode, uint64_t seed,
-                     const double *rand, double *trace_x, double *trace_lp,
-                     double *final_x, double *final_lp, int32_t reps,
-                     double *kernel_ms) {
-  if (check_ptr(x_obs, "x_obs") || check_ptr(y_obs, "y_obs") ||
-      check_ptr(hyper, "hyper") || check_ptr(init, "init"))
-    return PBH_ERR_ARG;
-  if (n_obs < 1 || n_obs > pbh::linreg_max_obs())
-    return fail(PBH_ERR_ARG, "n_obs must be in 1..%lld, got %lld",
-                (long long)pbh::linreg_max_obs(), (long long)n_obs);
-  if (n_chains < 1 || n_steps < 0 || step0 < 0 || chain_offset < 0)
-    return fail(PBH_ERR_ARG, "n_chains must be >= 1 and n_steps, step0, "
-                "chain_offset >= 0");
-  if (rng_mode != PBH_RNG_REPLAY && rng_mode != PBH_RNG_PHILOX &&
-      rng_mode != PBH_RNG_PHILOX_F64)
-    return fail(PBH_ERR_UNSUPPORTED, "pbh_linreg_gibbs: rng_mode %d", rng_mode);
-  if (rng_mode == PBH_RNG_REPLAY && n_steps > 0 && !rand)
-    return fail(PBH_ERR_ARG, "REPLAY needs rand [n_steps][n_chains]");
-  if (reps < 1) return fail(PBH_ERR_ARG, "reps must be >= 1");
-  if (hyper[1] == 0. || hyper[3] == 0.)
-    return fail(PBH_ERR_ARG, "prior sigmas must be non-zero");
-  const double alpha_post = hyper[4] + 0.5 * (double)n_obs;
-  if (!(alpha_post >= 1.))
-    return fail(PBH_ERR_ARG, "y_sigma_alpha + n_obs/2 must be >= 1");
-  pbh::LinregArgs h{};
-  std::vector<double> sq(n_obs);
-  // centred statistics for the FAST form, two passes in long double
-  long double mx = 0.L, my = 0.L;
-  for (int64_t j = 0; j < n_obs; ++j) {
-    sq[j] = x_obs[j] * x_obs[j];
-    mx += x_obs[j];
-    my += y_obs[j];
-  }
-  mx /= (long double)n_obs;
-  my /= (long double)n_obs;
-  long double cxx = 0.L, cxy = 0.L, cyy = 0.L;
-  for (int64_t j = 0; j < n_obs; ++j) {
-    const long double dx = x_obs[j] - mx, dy = y_obs[j] - my;
-    cxx += dx * dx;
-    cxy += dx * dy;
-    cyy += dy * dy;
-  }
-  h.hyper[0] = 1. / (hyper[1] * hyper[1]); h.hyper[1] = hyper[0];
-  h.hyper[2] = 1. / (hyper[3] * hyper[3]); h.hyper[3] = hyper[2];
-  h.hyper[4] = alpha_post; h.hyper[5] = hyper[5];
-  h.hyper[6] = np_pairwise_host(sq.data(), n_obs);
-  for (int k = 0; k < 3; ++k) {
-    if (vsets) {
-      if (!(vsets[2 * k] < vsets[2 * k + 1]))
-        return fail(PBH_ERR_ARG, "vsets[%d] must have lo < hi", k);
-      h.hyper[7 + k] = -std::log(vsets[2 * k + 1] - vsets[2 * k]);
-      h.bounds[2 * k] = vsets[2 * k];
-      h.bounds[2 * k + 1] = vsets[2 * k + 1];
-    } else {            // joint=False: no prior terms (lp + 0.0 == lp)
-      h.hyper[7 + k] = 0.;
-      h.bounds[2 * k] = -HUGE_VAL;
-      h.bounds[2 * k + 1] = HUGE_VAL;
-    }
-  }
-  h.hyper[10] = std::log(std::sqrt(2. * M_PI));
-  h.stats[0] = (double)mx; h.stats[1] = (double)my; h.stats[2] = (double)cxx;
-  h.stats[3] = (double)cxy; h.stats[4] = (double)cyy;
-  h.n_obs = n_obs; h.n = n_chains; h.chain_offset = chain_offset;
-  h.n_steps = n_steps; h.step0 = step0; h.seed = seed; h.mode = rng_mode;
-  if (kernel_ms) *kernel_ms = 0.;
-  HIP_TRY(hipSetDevice(device));
-  const int64_t T = n_steps, N = n_chains;
-  double *dxo = nullptr, *dyo = nullptr, *dinit = nullptr, *dstate = nullptr,
-         *dlp = nullptr, *drand = nullptr, *dtx = nullptr, *dtp = nullptr;
-  int rc = dalloc(dxo, n_obs);
-  if (!rc) rc = dalloc(dyo, n_obs);
-  if (!rc) rc = dalloc(dinit, 3 * N);
-  if (!rc) rc = dalloc(dstate, 3 * N);
-  if (!rc) rc = dalloc(dlp, N);
-  if (!rc && rng_mode == PBH_RNG_REPLAY && T > 0) rc = dalloc(drand, T * N);
-  if (!rc && T > 0 && trace_x) rc = dalloc(dtx, T * 3 * N);
-  if (!rc && T > 0 && trace_lp) rc = dalloc(dtp, T * N);
-  hipError_t err = hipSuccess;
-  hipStream_t st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  double total = 0.;
-  if (!rc) {
-    err = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipEventCreate(&e0);
-    if (err == hipSuccess) err = hipEventCreate(&e1);
-    if (err == hipSuccess) err = hipMemcpy(dxo, x_obs, n_obs * 8, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(dyo, y_obs, n_obs * 8, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(dinit, init, 3 * N * 8, hipMemcpyHostToDevice);
-    if (err == hipSuccess && drand)
-      err = hipMemcpy(drand, rand, T * N * 8, hipMemcpyHostToDevice);
-    h.x_obs = dxo; h.y_obs = dyo; h.state = dstate; h.lp_state = dlp;
-    h.rand = drand; h.tx = dtx; h.tp = dtp;
-    // r = 0 is an untimed warm-up launch, made only when timing several
-    // repetitions (a single run is the sampler's own)
-    for (int r = reps > 1 ? 0 : 1; r <= reps && err == hipSuccess && T > 0; ++r) {
-      err = hipMemcpyAsync(dstate, dinit, 3 * N * 8, hipMemcpyDeviceToDevice, st);
-      if (err == hipSuccess) err = hipEventRecord(e0, st);
-      if (err == hipSuccess) err = pbh::launch_linreg_gibbs(h, st);
-      if (err == hipSuccess) err = hipEventRecord(e1, st);
-      if (err == hipSuccess) err = hipEventSynchronize(e1);
-      float ms = 0.f;
-      if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
-      if (r > 0) total += ms;
-    }
-    if (err == hipSuccess && trace_x && T > 0)
-      err = hipMemcpy(trace_x, dtx, T * 3 * N * 8, hipMemcpyDeviceToHost);
-    if (err == hipSuccess && trace_lp && T > 0)
-      err = hipMemcpy(trace_lp, dtp, T * N * 8, hipMemcpyDeviceToHost);
-    if (err == hipSuccess && final_x)
-      err = hipMemcpy(final_x, T > 0 ? dstate : dinit, 3 * N * 8, hipMemcpyDeviceToHost);
-    if (err == hipSuccess && final_lp && T > 0)
-      err = hipMemcpy(final_lp, dlp, N * 8, hipMemcpyDeviceToHost);
-  }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  dfree(dxo); dfree(dyo); dfree(dinit); dfree(dstate); dfree(dlp);
-  dfree(drand); dfree(dtx); dfree(dtp);
-  if (rc) return rc;
-  if (err != hipSuccess)
-    return fail(PBH_ERR_HIP, "pbh_linreg_gibbs: %s", hipGetErrorString(err));
-  if (kernel_ms) *kernel_ms = total / reps;
   return PBH_OK;
 }
 

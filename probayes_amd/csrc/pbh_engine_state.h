@@ -1,7 +1,8 @@
 // pbh_engine_state.h -- what the units behind the C-ABI of include/pbhip.h
-// share (pbh_engine.hip, pbh_trace.cpp): the engine's state, the error
-// plumbing, device memory through the resource cache, and the two waits.
-// Internal: nothing here is part of the ABI.
+// share (pbh_engine.hip, pbh_trace.cpp, pbh_oneshot.cpp): the engine's state,
+// the error plumbing, device memory through the resource cache, the two
+// waits, and the host transposes between the caller's chain rows and the
+// device's dim-major arrays.  Internal: nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -197,6 +198,21 @@ int dgrow(T *&p, size_t &len, size_t need) {
   len = need;
   return PBH_OK;
 }
+
+// The caller's rows [n][d] (one chain or point after another) -> the device's
+// dim-major [d][n], and back; on the host.
+inline void rows_to_dim_major(const double *rows, double *dm, int64_t n, int64_t d) {
+  for (int64_t c = 0; c < n; ++c)
+    for (int64_t k = 0; k < d; ++k) dm[(size_t)k * n + c] = rows[(size_t)c * d + k];
+}
+inline void dim_major_to_rows(const double *dm, double *rows, int64_t n, int64_t d) {
+  for (int64_t c = 0; c < n; ++c)
+    for (int64_t k = 0; k < d; ++k) rows[(size_t)c * d + k] = dm[(size_t)k * n + c];
+}
+
+// PBH_EXPR_DATA_WIDE (pbh_oneshot.cpp): KArgs.ewide of pbh_set_model and of
+// the one-shot expression evaluator; not among the library's exported names
+__attribute__((visibility("hidden"))) int32_t expr_data_wide();
 
 // Ends the resident sampling server (pbh_engine.hip).  Every entry point that
 // touches the device state, the trace or the stream stops it first.

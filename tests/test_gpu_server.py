@@ -148,6 +148,51 @@ def test_server_command_time_and_sync(monkeypatch):
   eng.close()
 
 
+def test_a_run_the_server_may_not_take_stops_it_and_runs_as_launches(monkeypatch):
+  """Between commands, a run split into launches is no command: the server
+  stops, the run goes as launches, and the next eligible run relaunches it."""
+  def plan(eng, server):
+    eng.run(1)
+    eng.run(20)
+    if server:
+      assert eng.server_info()['active']
+    eng.run(40, steps_per_launch=16)
+    assert not eng.server_info()['active']
+    assert eng.last_run_ms()[1] == 3
+    eng.run(20)
+    return eng.server_info()
+  ref = _engine(monkeypatch, False)
+  plan(ref, False)
+  tr_ref, st_ref = ref.trace(), ref.state()
+  ref.close()
+  eng = _engine(monkeypatch, True)
+  info = plan(eng, True)
+  assert info['active'] and info['launches'] == 2 and info['commands'] == 2, info
+  tr, st = eng.trace(), eng.state()
+  eng.close()
+  for k in ('v_x', 'v_p', 'u'):
+    assert np.array_equal(tr[k], tr_ref[k]), k
+  assert np.array_equal(st[0], st_ref[0]) and np.array_equal(st[1], st_ref[1])
+
+
+def test_a_zero_step_run_leaves_the_server_as_it_is(monkeypatch):
+  eng = _engine(monkeypatch, True)
+  eng.run(1)
+  eng.run(20)
+  before = eng.server_info()
+  assert before['active'] and before['commands'] == 1, before
+  eng.run(0)
+  assert eng.server_info() == before
+  assert eng.last_run_ms() == (0., 0)
+  eng.run(0, sync=False)
+  assert eng.server_info() == before
+  eng.run(20)
+  info = eng.server_info()
+  assert info['active'] and info['commands'] == 2 and info['launches'] == 1, info
+  assert eng.trace_len() == 41
+  eng.close()
+
+
 EXIT_SCRIPT = r'''
 import os, sys
 sys.path.insert(0, {root!r})
