@@ -600,6 +600,41 @@ int pbh_trace_ess_rank(pbh_engine *eng, int64_t first, int64_t count,
                        double *bulk, double *tail, double *tail_parts,
                        double *basic, double *mean_acov);
 
+/* Pointwise log-likelihood over trace records [first, first + count) on the
+ * device, per observation (added within revision 2 as pbh_trace_rhat was:
+ * PBH_ABI_REVISION did not change for it, look the symbol up).  The program is
+ * a PBH_TARGET_EXPR program over data [n_cols][n_obs] of the pointwise shape:
+ * scalar words, one LOOP region, and that region's SUM as the last word
+ * (probayes_amd/expr.py trace_pointwise makes one of a callable that returns
+ * the unreduced vector of terms).  The body's last value at observation j and
+ * draw s = (record, chain) is the term T[s, j] (expr.evaluate_pointwise); the
+ * SUM is not formed.  Over the S = N count draws of the window, per
+ * observation (probayes_amd/diag.py pointwise_stats is the definition):
+ * lse [n_obs]: log sum_s exp T[s, j], shifted by the largest term -- -inf when
+ * every term is -inf, +inf with a +inf term, NaN with a NaN term; lppd_j is
+ * lse[j] - log S.
+ * mean [n_obs], var [n_obs]: the mean and the sample variance (ddof 1) of T[.,
+ * j]; the sum of var is WAIC's effective number of parameters.  A column that
+ * holds an infinite term has that infinity (or NaN for both) as its mean and a
+ * NaN variance.
+ * Each of the three may be NULL.  The program has nothing to do with the
+ * engine's model: it may be any target kind, its variables are the engine's
+ * dims (a variable index >= dim, or dim > PBH_EXPR_MAX_DIM, is PBH_ERR_ARG),
+ * and an engine whose own target is an expression program keeps it.  T is
+ * never stored: a workgroup folds the terms of 256 chains, 8 observations and
+ * a slice of the records into an online log-sum-exp pair and Welford's moments
+ * per lane, merges its lanes in a fixed order, and a second kernel merges the
+ * workgroups' rows in index order: no floating-point atomics, two calls give
+ * the same bits.  count >= 1 and N count >= 2; a bad program or one that is
+ * not of the pointwise shape is PBH_ERR_ARG, no trace PBH_ERR_STATE.  Changes
+ * nothing in the engine: not the model, the moments, the ESS, the trace, the
+ * chains or the generators.                                                 */
+int pbh_trace_pointwise(pbh_engine *eng, int64_t first, int64_t count,
+                        const int32_t *code, int32_t n_code,
+                        const double *consts, int32_t n_consts, int32_t depth,
+                        const double *data, int32_t n_cols, int32_t n_obs,
+                        double *lse, double *mean, double *var);
+
 /* ---- multi-GPU: one RCCL all-gather over xGMI --------- */
 int pbh_rccl_unique_id(uint8_t id[128]);
 int pbh_rccl_init(pbh_engine *eng, int32_t rank, int32_t world,

@@ -81,6 +81,21 @@ const char *expr_check(const ExprProgram &p, int *pc_out) {
   return nullptr;
 }
 
+const char *expr_pointwise_error(const ExprProgram &p, int *loop_pc) {
+  int loops = 0;
+  *loop_pc = -1;
+  for (int pc = 0; pc < p.n_code; ++pc)
+    if (expr_op((uint32_t)p.code[pc]) == PBH_EXPR_LOOP) {
+      if (loops++ == 0) *loop_pc = pc;
+      pc += expr_loop_len((uint32_t)p.code[pc]);   // a body word may look like anything
+    }
+  if (loops == 0) return "a pointwise program needs a loop region (it has none)";
+  if (loops > 1) return "a pointwise program has one loop region (it has several)";
+  if (*loop_pc + expr_loop_len((uint32_t)p.code[*loop_pc]) + 1 != p.n_code - 1)
+    return "a pointwise program ends in its region's SUM (words follow it)";
+  return nullptr;
+}
+
 // NumPy's pairwise_sum over the terms [s, s + m) (loops_utils.h: at most 128
 // terms are a leaf, else the left half rounded down to a multiple of 8, then
 // the rest); `pops`: the ancestors this subtree is the right child of.

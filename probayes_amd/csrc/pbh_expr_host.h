@@ -26,6 +26,10 @@ struct ExprProgram {
 // Every opcode, every operand's index for its kind, reads only after writes,
 // the regions, the limits (pbhip.h).  nullptr, or what is wrong (*pc: where).
 const char *expr_check(const ExprProgram &p, int *pc);
+// Whether a program that passed expr_check has the pointwise shape
+// (pbh_trace_pointwise): exactly one LOOP, and the region's SUM the last word.
+// nullptr and *loop_pc = where the LOOP word stands, or what is wrong.
+const char *expr_pointwise_error(const ExprProgram &p, int *loop_pc);
 // The leaves of np.sum over n_obs contiguous terms, in order (expr_leaf_word): NumPy's
 // pairwise sum of each buffer of 8192 terms, the buffers added one after another.
 // Returns the deepest stack of pending sums (<= kExprLeafStack to PBH_EXPR_MAX_OBS).

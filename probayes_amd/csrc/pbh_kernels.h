@@ -308,6 +308,20 @@ hipError_t launch_ess_spectrum(const double *base, int64_t n, int64_t stride, in
                                double *mean_first, double *mean_second, hipStream_t s);
 hipError_t launch_ess_finish(const double *part, int64_t n, const EssLayout &l, double *acov,
                              hipStream_t s);
+// The pointwise reduction (pbh_pointwise.hip): per observation the log-sum-exp,
+// the mean and the variance (ddof 1) over the n count draws of trace records
+// [first, first + count) of the term a pointwise program gives.  prog: the
+// program's block on the device as expr_pack laid it out (el), checked by
+// expr_check with the engine's d and by expr_pointwise_error (loop_pc).  l:
+// pointwise_layout's partition and offsets into scratch (pbh_trace_host.h).
+// Leaves lse, mean, var [3][l.npad] at scratch + l.res, the first n_obs of each
+// row written.  A fixed merge order, no floating-point atomics.
+struct ExprLayout;
+struct PointwiseLayout;
+hipError_t launch_pointwise(const double *tx, int64_t n, int32_t d, int64_t first, int64_t count,
+                            const double *prog, const ExprLayout &el, int32_t loop_pc,
+                            int32_t n_obs, unsigned char *scratch, const PointwiseLayout &l,
+                            hipStream_t s);
 // fft: 2 = the 2 048-point FFT form for count <= 1 536 records with the
 // 4 096-point form for the pairs it cannot decide (list: (d n + 1) / 2 + 1
 // int32 of device scratch), 1 = the 4 096-point form for count <= 2 048

@@ -8,6 +8,7 @@
 #include <initializer_list>
 
 #include "pbh_engine_state.h"
+#include "pbh_expr_host.h"
 #include "pbh_trace_host.h"
 
 using pbh::check_ptr;
@@ -458,6 +459,68 @@ int pbh_trace_ess_rank(pbh_engine *e, int64_t first, int64_t count, double *bulk
       const double a = ess[1][k], b = ess[2][k];
       tail[k] = a != a ? a : b != b ? b : b < a ? b : a;
     }
+  return PBH_OK;
+}
+
+int pbh_trace_pointwise(pbh_engine *e, int64_t first, int64_t count, const int32_t *code,
+                        int32_t n_code, const double *consts, int32_t n_consts, int32_t depth,
+                        const double *data, int32_t n_cols, int32_t n_obs, double *lse,
+                        double *mean, double *var) {
+  pbh::ExprProgram prog;
+  int loop_pc = -1;
+  const auto own = [&] {
+    if (e->cap <= 0 || !e->tx)
+      return fail(PBH_ERR_STATE, "no trace allocated (pbh_alloc_trace first)");
+    if (e->d > PBH_EXPR_MAX_DIM)
+      return fail(PBH_ERR_ARG, "pbh_trace_pointwise: the engine has %d dims, a program reads "
+                  "at most %d variables", (int)e->d, PBH_EXPR_MAX_DIM);
+    prog.d = (int32_t)e->d;
+    prog.code = code;
+    prog.n_code = n_code;
+    prog.consts = consts;
+    prog.n_consts = n_consts;
+    prog.depth = depth;
+    prog.data = data;
+    prog.n_cols = n_cols;
+    prog.n_obs = n_obs;
+    int pc = -1;
+    if (const char *bad = pbh::expr_check(prog, &pc))
+      return fail(PBH_ERR_ARG, "pbh_trace_pointwise: bad program at word %d: %s", pc, bad);
+    if (const char *bad = pbh::expr_pointwise_error(prog, &loop_pc))
+      return fail(PBH_ERR_ARG, "pbh_trace_pointwise: %s", bad);
+    return PBH_OK;
+  };
+  if (const int rc = trace_enter(e, {{code, "code"}}, false, first, count, 1, own)) return rc;
+  const int64_t n = e->n;
+  if (n < 2 && count < 2)
+    return fail(PBH_ERR_ARG, "pbh_trace_pointwise: %lld chain of %lld record: a variance needs "
+                "at least 2 draws", (long long)n, (long long)count);
+  std::vector<double> blk;
+  const pbh::ExprLayout el = pbh::expr_pack(blk, prog);
+  pbh::PointwiseLayout l;
+  if (!pbh::pointwise_layout(n, count, n_obs, 0, (int64_t)blk.size(), &l))
+    return fail(PBH_ERR_ARG, "pbh_trace_pointwise: no scratch layout for %lld chains of %lld "
+                "records", (long long)n, (long long)count);
+  HIP_TRY(hipSetDevice(e->device));
+  if (const int rc = scratch(e, (size_t)l.bytes)) return rc;
+  // the program in a block of its own in the reduction scratch: the model's
+  // ecode / econst / edata are not touched
+  double *dprog = at<double>(e->scratch, l.prog);
+  hipError_t err = hipMemcpyAsync(dprog, blk.data(), blk.size() * sizeof(double),
+                                  hipMemcpyHostToDevice, e->stream);
+  if (err == hipSuccess)
+    err = pbh::launch_pointwise(e->tx, n, (int32_t)e->d, first, count, dprog, el, loop_pc, n_obs,
+                                e->scratch, l, e->stream);
+  // (blk is the source of a queued copy: synchronised on every path)
+  const hipError_t drained = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess) err = drained;
+  const double *res = at<const double>(e->scratch, l.res);
+  double *const outs[3] = {lse, mean, var};
+  for (int v = 0; err == hipSuccess && v < 3; ++v)
+    if (outs[v])
+      err = hipMemcpy(outs[v], res + v * l.npad, (size_t)n_obs * sizeof(double),
+                      hipMemcpyDeviceToHost);
+  if (err != hipSuccess) return hip_fail("pbh_trace_pointwise", err);
   return PBH_OK;
 }
 

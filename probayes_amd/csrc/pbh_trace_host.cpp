@@ -177,4 +177,70 @@ double multi_chain_ess(const double *m, const double *A, int64_t C, int64_t h,
   return (double)C * (double)h / tau;
 }
 
+bool pointwise_layout(int64_t n, int64_t count, int32_t n_obs, int64_t select_words,
+                      int64_t prog_doubles, PointwiseLayout *out) {
+  int64_t draws;
+  if (n < 1 || count < 1 || n_obs < 1 || n_obs > PBH_EXPR_MAX_OBS || select_words < 0 ||
+      prog_doubles < 1 || prog_doubles > ((int64_t)1 << 40))
+    return false;
+  if (__builtin_mul_overflow(n, count, &draws)) return false;
+  PointwiseLayout l;
+  l.chain_blocks = n / kPointwiseLanes + (n % kPointwiseLanes != 0);
+  if (l.chain_blocks > 65535) return false;
+  l.tiles = ((int64_t)n_obs + kPointwiseTile - 1) / kPointwiseTile;
+  l.npad = l.tiles * kPointwiseTile;
+  const int64_t groups = l.chain_blocks * l.tiles;
+  const int64_t want = std::min(count, (kPointwiseGroups + groups - 1) / groups);
+  l.slice_len = (count + want - 1) / want;
+  l.slices = (count + l.slice_len - 1) / l.slice_len;
+  l.rows = l.chain_blocks * l.slices;
+  int64_t at = 0;
+  const auto take = [&at](int64_t bytes) {
+    const int64_t here = at;
+    at += (bytes + 255) / 256 * 256;
+    return here;
+  };
+  l.select = take(select_words * 8);
+  l.prog = take(prog_doubles * 8);
+  l.part = take(6 * l.rows * l.npad * 8);
+  l.res = take(3 * l.npad * 8);
+  l.bytes = at;
+  *out = l;
+  return true;
+}
+
+void pointwise_combine(const LsePair *lse, const Moments *mom, LsePair *lse_out,
+                       Moments *mom_out) {
+  LsePair fl[kPointwiseFold];
+  Moments fm[kPointwiseFold];
+  for (int t = 0; t < kPointwiseFold; ++t) {
+    fl[t] = lse[t];
+    fm[t] = mom[t];
+    for (int c = t + kPointwiseFold; c < kPointwiseLanes; c += kPointwiseFold) {
+      fl[t] = lse_merge(fl[t], lse[c]);
+      fm[t] = moments_merge(fm[t], mom[c]);
+    }
+  }
+  for (int w = kPointwiseFold / 2; w > 0; w >>= 1)
+    for (int t = 0; t < w; ++t) {
+      fl[t] = lse_merge(fl[t], fl[t + w]);
+      fm[t] = moments_merge(fm[t], fm[t + w]);
+    }
+  *lse_out = fl[0];
+  *mom_out = fm[0];
+}
+
+void pointwise_finish(const LsePair *lse, const Moments *mom, int64_t rows, double *lse_out,
+                      double *mean_out, double *var_out) {
+  LsePair l = lse_identity();
+  Moments m = moments_identity();
+  for (int64_t r = 0; r < rows; ++r) {
+    l = lse_merge(l, lse[r]);
+    m = moments_merge(m, mom[r]);
+  }
+  if (lse_out) *lse_out = lse_value(l);
+  if (mean_out) *mean_out = moments_mean(m);
+  if (var_out) *var_out = m.m2 / (m.n - 1.);
+}
+
 }  // namespace pbh

@@ -12,6 +12,8 @@
 #include <string>
 #include <vector>
 
+#include "pbh_pointwise_merge.h"
+
 namespace pbh {
 
 // Whether records [first, first + count) lie inside [0, rec) with count >=
@@ -94,5 +96,36 @@ bool ess_layout(int64_t n, int64_t count, int32_t d, int64_t base, int64_t selec
 // k_star (may be null): where the scan stopped.
 double multi_chain_ess(const double *m, const double *A, int64_t C, int64_t h,
                        int64_t *k_star = nullptr);
+
+// The pointwise reduction (pbh_pointwise.hip): the statistics over the draws
+// of a window of every observation's term.  A workgroup owns one block of
+// kPointwiseLanes chains, one tile of kPointwiseTile observations and one slice
+// of slice_len consecutive records (the last slice may be shorter); the record
+// slices are there to fill the device when chains and tiles are few: as many as
+// bring the grid to kPointwiseGroups workgroups, at most one per record.  Each
+// workgroup leaves one partial row, row = chain block * slices + slice, of npad
+// = 8 tiles observations.  The scratch, each offset a multiple of 256, the
+// regions disjoint and in this order: the select's own scratch (none today),
+// prog (the program's block as expr_pack lays it out, prog_doubles doubles),
+// part [6][rows][npad] (the maximum, the sum; the count, the shift, the mean
+// less the shift, M2) and res [3][npad] (lse, mean, var).
+constexpr int64_t kPointwiseGroups = 1024;
+struct PointwiseLayout {
+  int64_t chain_blocks, tiles, npad, slices, slice_len, rows;
+  int64_t select, prog, part, res, bytes;
+};
+// False when an argument is out of range (n, count < 1, n_obs outside 1 ..
+// PBH_EXPR_MAX_OBS, select_words < 0, prog_doubles < 1), n count leaves int64,
+// or the chain blocks exceed a grid's 65 535; `out` is then untouched.
+bool pointwise_layout(int64_t n, int64_t count, int32_t n_obs, int64_t select_words,
+                      int64_t prog_doubles, PointwiseLayout *out);
+// A workgroup's combination of its lanes' partials of one observation, lse and
+// mom [kPointwiseLanes], in the device's order (pbh_pointwise_merge.h).
+void pointwise_combine(const LsePair *lse, const Moments *mom, LsePair *lse_out,
+                       Moments *mom_out);
+// The finish: `rows` partial rows of one observation merged in index order,
+// then lse, mean and the variance at ddof 1 (any of the three may be null).
+void pointwise_finish(const LsePair *lse, const Moments *mom, int64_t rows, double *lse_out,
+                      double *mean_out, double *var_out);
 
 }  // namespace pbh

@@ -25,6 +25,11 @@ split_chain_acov, multi_chain_ess and rank_ess are the definition of the bulk-
 and tail-ESS of the same paper (pbh_trace_ess_rank, Engine.trace_ess_rank):
 the autocovariance averaged over the split chains, and Stan's estimator of the
 effective sample size from it.
+
+pointwise_stats and waic are the definition of the pointwise log-likelihood
+reduction (pbh_trace_pointwise, Engine.trace_pointwise): per observation the
+log-sum-exp, the mean and the variance over the draws of its term, and lppd,
+p_waic and WAIC from those (Watanabe 2010; Vehtari, Gelman & Gabry 2017).
 """
 import math
 
@@ -431,3 +436,43 @@ def rank_ess(x, first=0, count=None):
       res[key][k] = multi_chain_ess(m, acov, c_all, h)
   res['tail'] = np.minimum(res['tail_lower'], res['tail_upper'])
   return res
+
+
+def pointwise_stats(T):
+  """(lse [n], mean [n], var [n]) of the terms T [S, n] over the S >= 2 draws,
+  per observation j.  lse_j = log sum_s exp T[s, j] with scipy.special.
+  logsumexp's treatment of infinities: shifted by the column's maximum, taken
+  as 0 when that is not finite, so a column that is all -inf gives -inf, one
+  with a +inf gives +inf, and any NaN gives NaN.  mean_j is the mean and var_j
+  the sample variance (ddof 1) by two passes: the deviations from the mean,
+  then the mean of their squares over S - 1."""
+  T = np.asarray(T, float)
+  if T.ndim != 2 or T.shape[0] < 2:
+    raise ValueError('pointwise_stats: terms [S >= 2, n], got shape {}'.format(T.shape))
+  S = T.shape[0]
+  with np.errstate(all='ignore'):
+    top = T.max(axis=0)
+    top = np.where(np.isfinite(top), top, 0.)
+    lse = np.log(np.exp(T - top).sum(axis=0)) + top
+    mean = T.sum(axis=0) / S
+    dev = T - mean
+    var = (dev * dev).sum(axis=0) / (S - 1.)
+  return lse, mean, var
+
+
+def waic(lse, mean, var, S):
+  """WAIC from pointwise_stats' rows over S draws (Vehtari, Gelman & Gabry
+  2017): lppd_i = lse - log S, p_waic_i = var, elpd_i = lppd_i - p_waic_i per
+  observation; lppd, p_waic and elpd_waic their sums; se = sqrt(n var(elpd_i))
+  (np.var, ddof 0); waic = -2 elpd_waic.  mean is not read: it is there for the
+  call waic(*pointwise_stats(T), S)."""
+  lse, var = np.asarray(lse, float), np.asarray(var, float)
+  with np.errstate(all='ignore'):
+    lppd_i = lse - math.log(S)
+    p_waic_i = var
+    elpd_i = lppd_i - p_waic_i
+    elpd = float(elpd_i.sum())
+    return {'lppd_i': lppd_i, 'p_waic_i': p_waic_i, 'elpd_i': elpd_i,
+            'lppd': float(lppd_i.sum()), 'p_waic': float(p_waic_i.sum()),
+            'elpd_waic': elpd, 'se': float(np.sqrt(lse.size * np.var(elpd_i))),
+            'waic': -2. * elpd}

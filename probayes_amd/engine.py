@@ -756,6 +756,33 @@ class Engine:
                      if basic or key != 'basic'}
     return res
 
+  def trace_pointwise(self, program, first=0, count=None):
+    """Per observation, the statistics over the N count draws of trace records
+    [first, first + count) of the term a pointwise program gives, computed on
+    the device without the terms [draws, n_obs] ever being stored
+    (expr.evaluate_pointwise and diag.pointwise_stats are the definition):
+    {'lse': [n_obs], 'mean': [n_obs], 'var': [n_obs]} -- the log-sum-exp (lppd_j
+    = lse_j - log(N count)), the mean and the sample variance (ddof 1).
+    program: what expr.trace_pointwise returns, over this engine's dims in
+    order; it has nothing to do with the engine's own model, which may be of
+    any kind.  N count >= 2."""
+    first, count = self._window(first, count)
+    code = np.ascontiguousarray(program['code'], dtype=np.int32)
+    consts = _f64(program['consts']).ravel()
+    if consts.size == 0:
+      consts = np.zeros(1)
+    data = program.get('data')
+    data = None if data is None else np.atleast_2d(_f64(data))
+    n_cols, n_obs = (0, 0) if data is None else data.shape
+    out = np.empty((3, max(int(n_obs), 1)))
+    _lib.call('pbh_trace_pointwise', self._h, _c.c_int64(int(first)),
+              _c.c_int64(int(count)), _ip(code), _c.c_int32(code.size), _dp(consts),
+              _c.c_int32(np.asarray(program['consts']).size),
+              _c.c_int32(int(program['depth'])), None if data is None else _dp(data),
+              _c.c_int32(int(n_cols)), _c.c_int32(int(n_obs)),
+              _dp(out[0]), _dp(out[1]), _dp(out[2]))
+    return {'lse': out[0].copy(), 'mean': out[1].copy(), 'var': out[2].copy()}
+
   def rccl_allreduce_max(self, value):
     v = _c.c_double(float(value))
     _lib.call('pbh_rccl_allreduce_max', self._h, _c.byref(v))

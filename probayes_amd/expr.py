@@ -41,6 +41,14 @@ Loop regions (likelihoods summed over observed data)
   columns, 1 <= n <= MAX_OBS.  LOOP and SUM lie outside range(N_OPS): a
   program without data holds neither.
 
+Pointwise programs (statistics per observation over the trace)
+  trace_pointwise compiles a callable that returns the unreduced vector of
+  per-observation terms as the program of its sum: scalar words, one LOOP, the
+  body, and SUM as the last word.  The body's last value is the term;
+  evaluate_pointwise returns the terms [points, n], and the engine reduces
+  them over the draws of its trace (Engine.trace_pointwise) without forming
+  the sum.
+
 evaluate() below is the written definition of each opcode: a plain NumPy
 interpreter, vectorised over chains, whose loops are the ones the callable
 itself runs when it is called on arrays.
@@ -104,21 +112,11 @@ def _apply(op, va, fetch_b):
   return _BINARY[op](va, fetch_b())
 
 
-def evaluate(code, consts, x, data=None):
-  """The program at the points x [n, d] (or [d]) -> values [n] (or a scalar).
-  IEEE float64 throughout; POW is NumPy's `a ** c`.  data [C, n_obs]: the
-  columns the loop regions read.  A region's terms are laid out [points,
-  n_obs], C-contiguous, and reduced along the last axis: NumPy's pairwise sum
-  of each point's terms (a reduction along axis 0 would add rows in
-  sequence)."""
-  x = np.asarray(x, np.float64)
-  single = x.ndim == 1
-  x = np.ascontiguousarray(np.atleast_2d(x).T)   # [d, n]: contiguous columns
+def _run(code, consts, x, data, pointwise):
+  """evaluate / evaluate_pointwise at x [d, n] (contiguous columns): the
+  accumulator [n] after the last word, or with `pointwise` the terms [n, n_obs]
+  of the first region met."""
   n = x.shape[1]
-  consts = np.asarray(consts, np.float64)
-  if data is not None:
-    data = np.ascontiguousarray(np.atleast_2d(np.asarray(data, np.float64)))
-  code = [int(w) for w in np.asarray(code).reshape(-1)]
   slots = {}
   acc = None
 
@@ -132,8 +130,9 @@ def evaluate(code, consts, x, data=None):
       return consts[i]          # a float64 scalar, as in the callable
     return acc
 
-  def region(body):
-    """sum over the observations of the body's last value -> [n]"""
+  def terms(body):
+    """the body's last value at every point and observation -> [n, n_obs],
+    C-contiguous"""
     n_obs = data.shape[1]
     temps = {}
     bacc = None
@@ -154,8 +153,7 @@ def evaluate(code, consts, x, data=None):
       bacc = np.asarray(r, np.float64)
       if store:
         temps[dst] = bacc
-    terms = np.ascontiguousarray(np.broadcast_to(bacc, (n, n_obs)))
-    return np.add.reduce(terms, axis=1)
+    return np.ascontiguousarray(np.broadcast_to(bacc, (n, n_obs)))
 
   with np.errstate(all='ignore'):
     pc = 0
@@ -163,7 +161,11 @@ def evaluate(code, consts, x, data=None):
       op, dst, store, a, b = decode(code[pc])
       if op == LOOP:
         length = a[1]
-        r = region(code[pc + 1:pc + 1 + length])
+        t = terms(code[pc + 1:pc + 1 + length])
+        if pointwise:
+          return t
+        # the sum over the observations of the body's last value -> [n]
+        r = np.add.reduce(t, axis=1)
         pc += length + 1          # at the SUM word, which may store the sum
         op, dst, store, a, b = decode(code[pc])
       else:
@@ -172,7 +174,40 @@ def evaluate(code, consts, x, data=None):
       if store:
         slots[dst] = acc
       pc += 1
-  out = np.array(acc)
+  if pointwise:
+    raise ValueError('expr: a pointwise program needs a loop region')
+  return np.array(acc)
+
+
+def _points(code, consts, x, data):
+  x = np.asarray(x, np.float64)
+  single = x.ndim == 1
+  x = np.ascontiguousarray(np.atleast_2d(x).T)   # [d, n]: contiguous columns
+  consts = np.asarray(consts, np.float64)
+  if data is not None:
+    data = np.ascontiguousarray(np.atleast_2d(np.asarray(data, np.float64)))
+  code = [int(w) for w in np.asarray(code).reshape(-1)]
+  return code, consts, x, data, single
+
+
+def evaluate(code, consts, x, data=None):
+  """The program at the points x [n, d] (or [d]) -> values [n] (or a scalar).
+  IEEE float64 throughout; POW is NumPy's `a ** c`.  data [C, n_obs]: the
+  columns the loop regions read.  A region's terms are laid out [points,
+  n_obs], C-contiguous, and reduced along the last axis: NumPy's pairwise sum
+  of each point's terms (a reduction along axis 0 would add rows in
+  sequence)."""
+  code, consts, x, data, single = _points(code, consts, x, data)
+  out = _run(code, consts, x, data, False)
+  return out[0] if single else out
+
+
+def evaluate_pointwise(code, consts, x, data):
+  """The terms of a pointwise program (trace_pointwise) at the points x [n, d]
+  (or [d]) -> [n, n_obs] (or [n_obs]): what evaluate() sums in the program's
+  region, unreduced -- the same body loop, without the np.add.reduce."""
+  code, consts, x, data, single = _points(code, consts, x, data)
+  out = _run(code, consts, x, data, True)
   return out[0] if single else out
 
 
@@ -403,10 +438,8 @@ def _traced_updf(real):
   return updf
 
 
-def trace_expr(fn, keys):
-  """A scalar density callable over the variables `keys` -> {'kind': 'expr',
-  'code': int32[], 'consts': float64[], 'depth': int}, or NotLowerable.  A
-  density that sums over 1-D data arrays also carries 'data' [C, n]."""
+def _trace(fn, keys):
+  """fn called on symbolic variables under the patches: what it returned."""
   from probayes_amd.lower import NotLowerable, _patched
   d = len(keys)
   if d > MAX_DIM:
@@ -418,12 +451,20 @@ def trace_expr(fn, keys):
                 pdf=_traced_pdf(norm.pdf)), \
        _patched(unif, pdf=_traced_updf(unif.pdf)):
     try:
-      out = fn(**kw)
+      return fn(**kw)
     except NotLowerable:
       raise
     except Exception as e:
       raise NotLowerable('density callable not traceable: {}: {}'
                          .format(type(e).__name__, e))
+
+
+def trace_expr(fn, keys):
+  """A scalar density callable over the variables `keys` -> {'kind': 'expr',
+  'code': int32[], 'consts': float64[], 'depth': int}, or NotLowerable.  A
+  density that sums over 1-D data arrays also carries 'data' [C, n]."""
+  from probayes_amd.lower import NotLowerable
+  out = _trace(fn, keys)
   if not isinstance(out, Val):
     c = _const(out)
     if c is None:
@@ -433,7 +474,48 @@ def trace_expr(fn, keys):
   elif out.n:
     raise NotLowerable('density returned a vector of {} values unreduced (np.sum '
                        'or np.mean makes it a scalar)'.format(out.n))
-  return compile_dag(out, d)
+  return compile_dag(out, len(keys))
+
+
+def trace_pointwise(fn, keys):
+  """A callable of the variables `keys` that returns the unreduced vector of n
+  per-observation terms (a pointwise log-likelihood, a fitted value) -> the
+  program of its sum, {'kind': 'expr', 'code', 'consts', 'depth', 'data'} as
+  trace_expr gives it, of the pointwise shape: scalar words, LOOP, the body,
+  and SUM as the last word.  The body's last value is the term
+  (evaluate_pointwise; Engine.trace_pointwise reduces it over the trace)."""
+  from probayes_amd.lower import NotLowerable
+  out = _trace(fn, keys)
+  if isinstance(out, np.ndarray) and out.ndim:
+    out = _operand(out, 'the pointwise result')   # a data column as it is: a MOV
+  if not isinstance(out, Val):
+    if _const(out) is not None:
+      raise NotLowerable('pointwise function returned a scalar, already reduced: '
+                         'return the terms, not their sum')
+    raise NotLowerable('pointwise function returned {}, not a vector of terms'
+                       .format(type(out).__name__))
+  if not out.n:
+    if out.op == SUM or _under_sum(out):
+      raise NotLowerable('pointwise function returned a scalar, already reduced: '
+                         'return the terms, not their sum')
+    raise NotLowerable('pointwise function returned a scalar that depends on no '
+                       'data array: return one term per observation')
+  return compile_dag(Val(SUM, out), len(keys))
+
+
+def _under_sum(root):
+  """Whether a SUM node lies under the scalar node root."""
+  stack, seen = [root], set()
+  while stack:
+    v = stack.pop()
+    if not isinstance(v, Val) or id(v) in seen:
+      continue
+    seen.add(id(v))
+    if v.op == SUM:
+      return True
+    if not v.n:
+      stack += [v.a, v.b]
+  return False
 
 
 # ---------------------------------------------------------------------------

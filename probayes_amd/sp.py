@@ -1447,6 +1447,35 @@ class Sampler:
     return {key: {k: float(res[key][i]) for i, k in enumerate(self.names)}
             for key in ('bulk', 'tail', 'tail_lower', 'tail_upper')}
 
+  def trace_pointwise(self, fn, first=0, count=None):
+    """Per observation, the log-sum-exp, the mean and the variance over every
+    chain and every record [first, first + count) of the vector fn(**values)
+    returns -- a pointwise log-likelihood such as norm.logpdf(Y, b0 + b1 * X,
+    s), or any traced vector such as the fitted line b0 + b1 * X, whose mean
+    and variance are its posterior summary -- computed by the engine from its
+    device trace (Engine.trace_pointwise) without the [draws, observations]
+    terms ever being stored: {'lse': [n], 'mean': [n], 'var': [n]}.  fn takes
+    the sampler's names as keywords and returns the unreduced vector; it is
+    traced as a density is (expr.trace_pointwise; NotLowerable names what it
+    cannot hold).  Covers the sampler's first block while the engine still
+    holds it, as trace_quantile does."""
+    from probayes_amd import expr
+    first, count = self._device_window('trace_pointwise', first, count)
+    if self._eng.n * count < 2:
+      raise ValueError('trace_pointwise: {} chain of {} record: a variance needs '
+                       'at least 2 draws'.format(self._eng.n, count))
+    return self._eng.trace_pointwise(expr.trace_pointwise(fn, self.names), first, count)
+
+  def trace_waic(self, fn, first=0, count=None):
+    """WAIC of the pointwise log-likelihood fn over every chain and every
+    record [first, first + count) (trace_pointwise, then diag.waic with S = N
+    count draws): {'lppd', 'p_waic', 'elpd_waic', 'se', 'waic'} and the
+    per-observation rows 'lppd_i', 'p_waic_i', 'elpd_i'."""
+    from probayes_amd import diag
+    first, count = self._device_window('trace_waic', first, count)
+    res = self.trace_pointwise(fn, first, count)
+    return diag.waic(res['lse'], res['mean'], res['var'], self._eng.n * count)
+
   def trace_quantile_pooled(self, q, first=0, count=None):
     """The posterior quantiles q of every name, pooled over every chain and
     every record [first, first + count), computed by the engine from its
