@@ -108,7 +108,11 @@ def _apply(op, va, fetch_b):
     return _UNARY[op](va)
   if op == POW:
     vb = fetch_b()
-    return va ** (float(vb) if np.ndim(vb) == 0 else vb)
+    if np.ndim(va) == 0 and np.ndim(vb) == 0:
+      return va ** float(vb)     # scalars: C's pow, as the callable's own `**`
+    # arrays: the pow ufunc, not `array ** scalar`, whose fast paths for the
+    # exponents 0.5, -1, 1 and 2 (sqrt, reciprocal, copy, square) are not pow
+    return np.power(va, vb)
   return _BINARY[op](va, fetch_b())
 
 
@@ -192,7 +196,10 @@ def _points(code, consts, x, data):
 
 def evaluate(code, consts, x, data=None):
   """The program at the points x [n, d] (or [d]) -> values [n] (or a scalar).
-  IEEE float64 throughout; POW is NumPy's `a ** c`.  data [C, n_obs]: the
+  IEEE float64 throughout; POW is pow(a, c) (np.power: C99's special values,
+  pow(-0., 0.5) = +0. and pow(-inf, 0.5) = +inf, as the device's pow and as
+  `a ** c` on scalars; not `array ** c`, which NumPy rewrites to sqrt,
+  reciprocal or square for c = 0.5, -1, 2).  data [C, n_obs]: the
   columns the loop regions read.  A region's terms are laid out [points,
   n_obs], C-contiguous, and reduced along the last axis: NumPy's pairwise sum
   of each point's terms (a reduction along axis 0 would add rows in
