@@ -18,7 +18,20 @@ Conventions read from the code (pbh_engine.hip, pbh_kernels_impl.h):
     (chain >> 32) ^ ((g >> 32) << 16)), j the block index of a role;
   * the lane-pair kernel (mh_pair_kernel, even d >= 4): lane half h owns the
     dims [h H, h H + H), H = d / 2, and draws them from blocks q + 16 h; half
-    1 holds the threshold and decides (its lead, tail block 0x40 + 16).
+    1 holds the threshold and decides (its lead, tail block 0x40 + 16);
+  * the production Gibbs kernel (gibbs_fast_kernel, d <= 16, L = 1, 2 or 4
+    lanes per chain, M = d / L): step g updates the coordinates [(g % nblk)
+    tsteps, min(d, ... + tsteps)), nblk = ceil(d / tsteps); every draw of a
+    coordinate cycle is keyed by the cycle's FIRST step gc = g - g % nblk,
+    whichever launch or step consumes it.  Coordinate k = p M + ii takes
+    component ii % 2 of the Box-Muller pair (box_muller(): u1 = 1 - u01(x, y),
+    u2 = u01(z, w); the device's box_muller_tab approximates it) of block
+    0x100 + 16 p + ii / 2 at (gc, chain).  A normal outside [ndtri(cdf_lo_k),
+    ndtri(cdf_hi_k)] is replaced by ndtri(cdf_lo + (cdf_hi - cdf_lo) u), u =
+    u01(w.x, w.y) of block 0x200 + k at (gc, chain);
+  * the ndtri Gibbs kernel (gibbs_kernel: d > 16, PBH_GIBBS_FAST=0 or debug
+    records): the j-th coordinate a step g updates takes u01(w.x, w.y) of
+    block j at (g, chain), the step itself, not the cycle.
 
 Draw functions return (r [T, d, N], thr [T, N], blocks) for the absolute steps
 g0 .. g0 + T - 1 and chain ids chain_offset .. chain_offset + N - 1; blocks is
@@ -314,3 +327,89 @@ def f64_draws(seed, d, g0, T, chain_offset, N, kind='gauss', pair=False):
 def streams(r, thr):
   """(r, thr) as the replay layout [T, d + 1, N] of oracle.run_mh."""
   return np.concatenate([r, thr[:, None, :]], axis=1)
+
+
+# ---------------------------------------------------------------------------
+# the CondCov Gibbs kernels
+# ---------------------------------------------------------------------------
+GIBBS_NORMALS = 0x100   # + 16 p + ii / 2: the Box-Muller pairs of part p
+GIBBS_INVERT = 0x200    # + k: coordinate k's inversion uniform
+GIBBS_MAX_D = 16        # gibbs_fast_form: d <= 16
+
+
+def gibbs_layout(d, L):
+  """gibbs_fast_kernel<d, L>: ([(block, pair component)] of every
+  coordinate's normal, [inversion block] of every coordinate)."""
+  assert L in (1, 2, 4) and d % L == 0
+  M = d // L
+  normals = [(GIBBS_NORMALS + 16 * (k // M) + (k % M) // 2, (k % M) % 2)
+             for k in range(d)]
+  return normals, [GIBBS_INVERT + k for k in range(d)]
+
+
+def gibbs_lanes(d, env=None):
+  """Lanes per chain as launch_gibbs_d chooses them: PBH_GIBBS_LANES when it
+  is 1, 2 or 4 and divides d, else 1 for odd d, 2 for even d <= 12, and
+  above that 4 where 4 divides d (2 where it does not)."""
+  import os
+  default = 1 if d % 2 else (2 if d <= 12 else (4 if d % 4 == 0 else 2))
+  text = (os.environ if env is None else env).get('PBH_GIBBS_LANES')
+  try:
+    want = int(text) if text is not None else 0      # the engine reads it with atoi
+  except ValueError:
+    want = 0
+  return want if want in (1, 2, 4) and d % want == 0 else default
+
+
+def gibbs_lane_choices(d):
+  """Every L the kernel can take at d."""
+  return [L for L in (1, 2, 4) if d % L == 0]
+
+
+def gibbs_cycle_starts(d, tsteps, g0, T):
+  """(nblk, [gc of steps g0 .. g0 + T - 1])."""
+  nblk = -(-d // tsteps)
+  return nblk, [g - g % nblk for g in range(int(g0), int(g0) + T)]
+
+
+def gibbs_fast_draws(seed, d, L, tsteps, g0, T, chain_offset, N):
+  """gibbs_fast_kernel's draws for the steps g0 .. g0 + T - 1: z [T, d, N],
+  the d Box-Muller normals of each step's coordinate cycle, and u_inv [T, d,
+  N], the inversion uniforms of that cycle (steps of one cycle share both)."""
+  _, gcs = gibbs_cycle_starts(d, tsteps, g0, T)
+  uniq = sorted(set(gcs))
+  at = {gc: i for i, gc in enumerate(uniq)}
+  g = np.array(uniq, dtype=np.uint64)[:, None]
+  chain = (np.uint64(int(chain_offset)) + np.arange(N, dtype=np.uint64))[None, :]
+  normals, invert = gibbs_layout(d, L)
+  z = np.empty((len(uniq), d, N))
+  u = np.empty((len(uniq), d, N))
+  pairs = {}
+  for k in range(d):
+    j, comp = normals[k]
+    if j not in pairs:
+      pairs[j] = box_muller(block(seed, j, g, chain))
+    z[:, k] = pairs[j][comp]
+    w = block(seed, invert[k], g, chain)
+    u[:, k] = u01(w[0], w[1])
+  idx = np.array([at[gc] for gc in gcs])
+  return z[idx], u[idx]
+
+
+def gibbs_uniform_streams(seed, d, tsteps, g0, T, chain_offset, N):
+  """gibbs_kernel's Philox uniforms as the replay layout [T, tsteps, N] of
+  oracle.run_gibbs: u01(w.x, w.y) of block j at (g, chain) for the j-th
+  coordinate of step g (a short last block leaves its spare rows unread)."""
+  g, chain = _grid(g0, T, chain_offset, N)
+  out = np.empty((T, tsteps, N))
+  for j in range(tsteps):
+    w = block(seed, j, g, chain)
+    out[:, j] = u01(w[0], w[1])
+  return out
+
+
+def gibbs_blocks(d, L, tsteps):
+  """The three block sets a Gibbs run of this shape can touch: the normals',
+  the inversion draws' and gibbs_kernel's 0 .. tsteps - 1."""
+  normals, invert = gibbs_layout(d, L)
+  return {j for j, _ in normals}, set(invert), set(range(tsteps))

@@ -11,7 +11,10 @@ Forms covered (thin 1, trace allocated): the lane-pair kernel in its
 steady-state and general forms and at the ends of its d range, cfg1's
 one-lane steady-state kernel, the GMM quad kernel (8- and 4-step groups, and
 its general form), the GMM lane-pair kernel, the general mh_kernel with
-Gaussian and with uniform draws (d = 1 takes the lead from another word), the
+Gaussian and with uniform draws (d = 1 takes the lead from another word), a
+covariance-matrix random walk on either stream (golden covrw5: a spherical
+delta, uniform draws, odd d; test_gpu_covrw's d = 10 Gaussian one: measured
+v_x 5.0e-16, v_p 4.2e-16, score 1.5e-14, no tie, accept rates 0.55 / 0.66), the
 expression kernels (d = 3, a scratch-free d = 12, a d = 9 data program), the
 same models in PBH_RNG_PHILOX_F64 (there also whole chains against
 oracle.run_mh), chain ids straddling 2^32 and a step origin straddling 2^32.
@@ -308,6 +311,30 @@ def test_mh_kernel_uniform_draws(kind, d):
   init = np.stack([rs.uniform(-0.9, 0.9, 65), rs.uniform(-0.9, 0.9, 65),
                    rs.uniform(0.1, 1.9, 65)], 1)[:, :d]
   _pin(spec, init, 'uniform')
+
+
+# ---------------------------------------------------------------------------
+# 8b: a covariance-matrix random walk (proposal['tfun']) on the general mh_kernel
+# ---------------------------------------------------------------------------
+def _covrw_case(which):
+  """covrw5: odd d, a spherical delta (uniform draws) times chol(cov).
+  spec10: test_gpu_covrw's d = 10 Gaussian delta times chol(cov10); with a
+  tfun it is no lane-pair form, so mh_kernel's step_draws stream feeds it."""
+  if which == 'covrw5':
+    return oracle.golden_spec('covrw5'), 'uniform'
+  from test_gpu_covrw import _spec10
+  return _spec10(), 'step'
+
+
+@pytest.mark.parametrize('debug', [True, False])
+@pytest.mark.parametrize('which', ['covrw5', 'spec10'])
+def test_mh_kernel_covariance_random_walk(which, debug):
+  """eval_delta multiplies the base delta by the tfun after check_steps'
+  order line has given dim k the k-th draw, which is the kernel's order
+  (apply_tfun on dl[0 .. d-1]): no further permutation is needed."""
+  spec, contract = _covrw_case(which)
+  spec = _norm(spec)
+  _pin(spec, _spread(spec, 65, 14), contract, debug=debug)
 
 
 # ---------------------------------------------------------------------------

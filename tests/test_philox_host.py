@@ -1,6 +1,10 @@
 """The host restatement of the Philox draw contracts (tests/philox_host.py):
 known answers of the generator, no block drawn twice by any contract, and
-the threshold's bits disjoint from the proposal's bits."""
+the threshold's bits disjoint from the proposal's bits.  For the CondCov Gibbs
+kernels: the block sets of the normals, the inversion uniforms and the ndtri
+kernel's uniforms are disjoint and serve every coordinate once, the lane rule
+is launch_gibbs_d's, and the host model of tests/test_gpu_gibbs_pin.py equals
+oracle.gibbs.run_gibbs over whole chains; its checker bites."""
 import numpy as np
 import pytest
 
@@ -192,3 +196,155 @@ def test_checker_accepts_the_oracle_chain_and_bites():
   moved = dict(trace, v_p=np.where(ref['u'] == 0, np.nextafter(ref['v_p'], 0.), ref['v_p']))
   with pytest.raises(AssertionError):     # a rejected step must keep its record's bits
     check_steps(spec, moved, r, thr, init)
+
+
+# ---------------------------------------------------------------------------
+# the CondCov Gibbs kernels' contract
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize('d', range(1, 17))
+def test_gibbs_blocks_are_disjoint_and_serve_every_coordinate_once(d):
+  for L in ph.gibbs_lane_choices(d):
+    normals, invert = ph.gibbs_layout(d, L)
+    # every coordinate has a (block, component) and an inversion block of its own
+    assert len(normals) == d and len(set(normals)) == d
+    assert all(c in (0, 1) for _, c in normals)
+    assert invert == [ph.GIBBS_INVERT + k for k in range(d)]
+    M = d // L
+    for k, (j, c) in enumerate(normals):
+      assert (j, c) == (ph.GIBBS_NORMALS + 16 * (k // M) + (k % M) // 2, (k % M) % 2)
+    # a part's pairs stay below the next part's base
+    assert (M + 1) // 2 <= 16
+    for tsteps in range(1, d + 1):
+      a, b, c = ph.gibbs_blocks(d, L, tsteps)
+      assert not (a & b) and not (a & c) and not (b & c), (d, L, tsteps)
+      assert len(b) == d and len(c) == tsteps and len(a) == L * ((M + 1) // 2)
+  # d = 1 .. 16 never meets the MH kernels' tail blocks either
+  assert ph.TAIL_STEP not in a | b and ph.TAIL_PAIR not in a | b
+
+
+def test_gibbs_lanes_rule():
+  for d in range(1, 17):
+    want = 1 if d % 2 else (2 if d <= 12 else (4 if d % 4 == 0 else 2))
+    assert ph.gibbs_lanes(d, {}) == want
+    for L in (1, 2, 4):
+      got = ph.gibbs_lanes(d, {'PBH_GIBBS_LANES': str(L)})
+      assert got == (L if d % L == 0 else want)
+    for bad in ('3', '8', '0', '-2', 'x', ''):
+      assert ph.gibbs_lanes(d, {'PBH_GIBBS_LANES': bad}) == want
+  assert [ph.gibbs_lanes(d, {}) for d in (8, 14, 16)] == [2, 2, 4]
+
+
+def test_gibbs_draws_are_keyed_by_the_cycle_start():
+  """Steps of one cycle share the cycle's draws, whatever step a window starts
+  at; the uniforms of gibbs_kernel are keyed by the step itself."""
+  seed, d, L, n = 99, 6, 2, 3
+  z, u = ph.gibbs_fast_draws(seed, d, L, 1, 0, 18, 7, n)
+  assert np.array_equal(z[0], z[5]) and np.array_equal(u[6], u[11])
+  assert not np.array_equal(z[5], z[6])
+  z2, u2 = ph.gibbs_fast_draws(seed, d, L, 1, 4, 9, 7, n)      # a mid-cycle origin
+  assert np.array_equal(z2, z[4:13]) and np.array_equal(u2, u[4:13])
+  # tsteps = 4: nblk = 2, cycles start at even steps
+  z4, _ = ph.gibbs_fast_draws(seed, d, L, 4, 0, 4, 7, n)
+  assert np.array_equal(z4[0], z4[1]) and np.array_equal(z4[0], z[0])
+  assert np.array_equal(z4[2], z4[3]) and not np.array_equal(z4[2], z4[0])
+  # by hand: coordinate 4 = part 1, ii = 1 -> component 1 of block 0x100 + 16
+  chain = np.array([[7, 8, 9]], np.uint64)
+  z0, z1 = ph.box_muller(ph.block(seed, 0x110, np.array([[6]], np.uint64), chain))
+  assert np.array_equal(z[6, 4], z1[0]) and np.array_equal(z[6, 3], z0[0])
+  w = ph.block(seed, 0x204, np.array([[6]], np.uint64), chain)
+  assert np.array_equal(u[8, 4], ph.u01(w[0], w[1])[0])
+  s = ph.gibbs_uniform_streams(seed, d, 4, 5, 3, 7, n)
+  w = ph.block(seed, 2, np.array([[6]], np.uint64), chain)
+  assert s.shape == (3, 4, n) and np.array_equal(s[1, 2], ph.u01(w[0], w[1])[0])
+
+
+def _anchor_spec(d, tsteps, lo, hi):
+  from test_gpu_gibbs_fast import _spec_d
+  from test_gpu_gibbs_pin import _norm2d
+  if d == 2:
+    return _norm2d(lo, hi, tsteps)
+  spec = _spec_d(d, 7, lo, hi)
+  spec['proposal']['tsteps'] = tsteps
+  return spec
+
+
+ANCHOR = [(3, 1, 1, -1., 1.5), (2, 2, 2, -0.5, 1.), (8, 2, 1, -1.5, 2.), (4, 4, 3, -1.5, 2.)]
+
+
+@pytest.mark.parametrize('d,L,tsteps,lo,hi', ANCHOR)
+def test_gibbs_host_model_equals_the_oracle(d, L, tsteps, lo, hi):
+  """Whole chains of the host model (tests/test_gpu_gibbs_pin.py) equal
+  oracle.gibbs.run_gibbs on the equivalent uniforms: (ndtr(z) - cdf_lo) /
+  (cdf_hi - cdf_lo) where the normal lies inside the limits, the inversion
+  uniform where it does not.  1e-12 absolute at |x| = O(1); the round trip
+  ndtri(ndtr(z)) costs under eps / phi(2.8) = 3e-14 with every |zlim| <= 2.8.
+  Measured: 3.6e-15, 1.1e-15, 4.0e-15, 9.3e-15 with 263, 1 002, 154, 205
+  inversion draws."""
+  import oracle.gibbs
+  import scipy.stats
+  from test_gpu_gibbs_pin import host_chain, tables, _init
+  spec = _anchor_spec(d, tsteps, lo, hi)
+  tb = tables(spec)
+  # (d = 4 has one limit at 3.06: eps / phi(3.06) = 6e-14, still a tenth of the bar)
+  zmax = max(np.abs(tb.zlo).max(), np.abs(tb.zhi).max())
+  assert np.finfo(float).eps / scipy.stats.norm.pdf(zmax) <= 1e-13, zmax
+  n, t = 24, 40
+  init = _init(spec, n, d)
+  vx, streams, n_inv = host_chain(spec, L, init, t)
+  assert 0 < n_inv < streams.size and np.all((streams >= 0) & (streams < 1))
+  ref = oracle.gibbs.run_gibbs(spec, init, streams)
+  err = float(np.max(np.abs(vx - ref['v_x'])))
+  print('d {} L {} tsteps {}: {} inversion draws, max abs err {:.3g}'.format(
+      d, L, tsteps, n_inv, err))
+  assert err <= 1e-12, err
+
+
+def test_gibbs_checker_accepts_the_host_chain_and_bites():
+  """check_gibbs_steps on a trace the host model made passes with zero
+  error; a trace made with another lane layout, with a pair's components
+  swapped, with the step in place of the cycle start, or with a moved v_p,
+  accept word or untouched coordinate fails."""
+  from test_gpu_gibbs_fast import _spec_d
+  import scipy.special
+  from test_gpu_gibbs_pin import check_gibbs_steps, host_trace, ndtri_mp, _init
+  for p in (1e-3, 0.0668, 0.3, 0.5, 0.77, 0.9772, 0.997):
+    z = ndtri_mp(p)
+    assert abs(z - scipy.special.ndtri(p)) <= 1e-15 * max(1., abs(z)), p
+  spec = _spec_d(8, 7, -1.5, 2.)
+  n, t = 37, 48
+  init = _init(spec, n, 8)
+  trace = host_trace(spec, 2, init, t)
+  out = check_gibbs_steps(spec, trace, 2, init)
+  assert out['ties'] == 0 and out['v_x_bm'] == 0. and out['v_x_inv'] == 0.
+  assert out['v_p'] == 0. and 0.02 <= out['share'][0] <= out['share'][1] <= 0.98
+  for L in (1, 4):                                   # another routing of the same draws
+    with pytest.raises(AssertionError):
+      check_gibbs_steps(spec, trace, L, init)
+  orig = ph.box_muller
+  try:
+    ph.box_muller = lambda blk: orig(blk)[::-1]      # z0 and z1 swapped
+    with pytest.raises(AssertionError):
+      check_gibbs_steps(spec, trace, 2, init)
+  finally:
+    ph.box_muller = orig
+  starts = ph.gibbs_cycle_starts
+  try:                                               # keyed by the step, not the cycle start
+    ph.gibbs_cycle_starts = lambda d, ts, g0, T: (-(-d // ts), list(range(g0, g0 + T)))
+    with pytest.raises(AssertionError):
+      check_gibbs_steps(spec, trace, 2, init)
+  finally:
+    ph.gibbs_cycle_starts = starts
+  bad = dict(trace, v_p=trace['v_p'] * (1 + 3e-9))
+  with pytest.raises(AssertionError):
+    check_gibbs_steps(spec, bad, 2, init)
+  words = trace['acc_words'].copy()
+  words[5, 0] |= np.uint64(1) << np.uint64(n)        # a bit past the last chain
+  with pytest.raises(AssertionError):
+    check_gibbs_steps(spec, dict(trace, acc_words=words), 2, init)
+  vx = trace['v_x'].copy()
+  vx[3, 9, 5] = np.nextafter(vx[3, 9, 5], 9.)        # step 9 updates coordinate 1 only
+  with pytest.raises(AssertionError):
+    check_gibbs_steps(spec, dict(trace, v_x=vx), 2, init)
+  mom = dict(trace['moments'], n_acc=trace['moments']['n_acc'] - 1)
+  with pytest.raises(AssertionError):
+    check_gibbs_steps(spec, dict(trace, moments=mom), 2, init)
