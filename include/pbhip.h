@@ -635,6 +635,42 @@ int pbh_trace_pointwise(pbh_engine *eng, int64_t first, int64_t count,
                         const double *data, int32_t n_cols, int32_t n_obs,
                         double *lse, double *mean, double *var);
 
+/* The tail of the pointwise terms over trace records [first, first + count)
+ * on the device, per observation: what Pareto-smoothed importance sampling
+ * (PSIS-LOO: Vehtari, Gelman & Gabry 2017; Vehtari et al. 2024) needs of the
+ * terms T[s, j] of pbh_trace_pointwise, which are never stored (added within
+ * revision 2 as pbh_trace_pointwise was: look the symbol up).  The program and
+ * data arguments are pbh_trace_pointwise's.  Over the S = N count draws
+ * (probayes_amd/diag.py pointwise_tail is the definition):
+ * tail [n_obs][k]: the k smallest terms of observation j, ascending -- the k
+ * largest importance log-ratios -T -- either zero as +0.0 and NaN, the largest
+ * in the order, last.
+ * rest_lse [n_obs]: log sum exp(-T[s, j]) over the other S - k draws, with
+ * pbh_trace_pointwise's conventions: -inf when every one of them is +inf, +inf
+ * with a -inf term among them, NaN with a NaN.
+ * passes (may be NULL): the count passes run, the most of any batch.
+ * A most-significant-digit radix select on the monotone 64-bit image of a
+ * double, one select per observation, 10 bits a pass, the terms recomputed in
+ * every pass: the device counts the next digit under every observation's
+ * prefix (integer atomics), the host picks the digit that holds rank k - 1;
+ * once the keys at or below the prefix fit `capacity` per observation (0: max(2
+ * k, 65 536), no more than S), or all 64 bits are fixed, one more pass appends
+ * them to per-observation lists and folds minus every other term into an
+ * online log-sum-exp, merged in pbh_trace_pointwise's fixed order.  The host
+ * sorts each list: the first k are the tail, the others join the rest in
+ * ascending order.  The order in which the lists were filled is lost in the
+ * sort and no floating-point atomic is used: two calls give the same bits.
+ * The observations are taken in batches, so that the lists hold at most 256
+ * MiB whatever n_obs is.  1 <= k < N count; capacity >= k or 0, at most 4 194
+ * 304; tail or rest_lse may be NULL, not both (PBH_ERR_ARG); other errors as
+ * pbh_trace_pointwise.  Changes nothing in the engine.                       */
+int pbh_trace_pointwise_tail(pbh_engine *eng, int64_t first, int64_t count,
+                             const int32_t *code, int32_t n_code,
+                             const double *consts, int32_t n_consts,
+                             int32_t depth, const double *data, int32_t n_cols,
+                             int32_t n_obs, int64_t k, int64_t capacity,
+                             double *tail, double *rest_lse, int32_t *passes);
+
 /* ---- multi-GPU: one RCCL all-gather over xGMI --------- */
 int pbh_rccl_unique_id(uint8_t id[128]);
 int pbh_rccl_init(pbh_engine *eng, int32_t rank, int32_t world,

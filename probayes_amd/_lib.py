@@ -176,6 +176,13 @@ SIGNATURES = {
                                            ctypes.c_int32, ctypes.c_int32, _dp,
                                            ctypes.c_int32, ctypes.c_int32, _dp, _dp,
                                            _dp]),
+    # (likewise within revision 2)
+    'pbh_trace_pointwise_tail': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_int64, _ip, ctypes.c_int32, _dp,
+                                                ctypes.c_int32, ctypes.c_int32, _dp,
+                                                ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_int64, ctypes.c_int64, _dp, _dp,
+                                                _i32p]),
     'pbh_trace_ess':(ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
                                      ctypes.c_int64, _dp]),
     'pbh_rccl_allreduce_max': (ctypes.c_int, [ctypes.c_void_p, _dp]),

@@ -322,6 +322,29 @@ hipError_t launch_pointwise(const double *tx, int64_t n, int32_t d, int64_t firs
                             const double *prog, const ExprLayout &el, int32_t loop_pc,
                             int32_t n_obs, unsigned char *scratch, const PointwiseLayout &l,
                             hipStream_t s);
+// The tail select of the pointwise terms (pbh_pointwise_tail.hip), one batch of
+// observation tiles at a time: tile0 its first tile, pl the pointwise_layout of
+// the batch's observations (its select region tl's words: tail_layout,
+// pbh_trace_host.h), the program and the window as launch_pointwise takes them.
+// launch_tail_count clears the histograms and counts, under the prefixes at
+// tl.prefix, the digit after the `done` bits fixed so far; launch_tail_gather
+// clears the cursors, appends the candidates to the lists (never past
+// capacity) and leaves the partial pairs of the other terms, negated, at pl.part
+// [2][rows][npad] (the maximum, the sum).  Integer atomics only.
+struct TailLayout;
+struct TailLaunch {
+  const double *tx;
+  int64_t n, first, count;
+  int32_t d, loop_pc, n_obs, tile0;
+  const double *prog;
+  const ExprLayout *el;
+  unsigned char *scratch;
+  const PointwiseLayout *pl;
+  const TailLayout *tl;
+  int64_t capacity;
+};
+hipError_t launch_tail_count(const TailLaunch &t, int32_t done, hipStream_t s);
+hipError_t launch_tail_gather(const TailLaunch &t, int32_t done, hipStream_t s);
 // fft: 2 = the 2 048-point FFT form for count <= 1 536 records with the
 // 4 096-point form for the pairs it cannot decide (list: (d n + 1) / 2 + 1
 // int32 of device scratch), 1 = the 4 096-point form for count <= 2 048

@@ -27,48 +27,21 @@
 //       tile at or past n_obs (computed on the columns' zero padding) have
 //       partials and no result.
 //
+// The workgroup's place in the grid, the walk over its records and the lanes'
+// merge are pbh_pointwise_impl.h's, shared with the tail select
+// (pbh_pointwise_tail.hip).
+//
 // Every order is fixed, so two calls give the same bits.  -ffp-contract=off,
 // and the unit goes through the E64 pass, as the expression units do.
-#include "pbh_expr_host.h"
-#include "pbh_expr_impl.h"
-#include "pbh_trace_host.h"
+#include "pbh_pointwise_impl.h"   // the group, the walk and the lanes' merge
 
 namespace pbh {
 namespace {
 
-static_assert(kPointwiseLanes == kBlock && kPointwiseTile == kW, "one lane layout");
-static_assert(kExprTemps * kW >= 4 * kPointwiseTile, "the partials fit the temporaries");
-
-struct PointwiseArgs {
-  const double *tx;          // the trace [record][d][n]
-  int64_t n, first, count;   // chains, the window
-  int64_t slice_len, slices, rows, npad;
-  int32_t d, loop_pc, body_len;
-  double *part;              // [6][rows][npad]
-};
-
-constexpr int D = PBH_EXPR_MAX_DIM;
-
-__device__ __forceinline__ void load_draw(const PointwiseArgs &p, int64_t r, int64_t c,
-                                          double (&x)[D]) {
-  const double *at = p.tx + (p.first + r) * p.d * p.n + c;
-#pragma unroll
-  for (int k = 0; k < D; ++k) x[k] = k < p.d ? at[k * p.n] : 0.;
-}
-
 __global__ __launch_bounds__(kBlock) void pointwise_kernel(KArgs a, PointwiseArgs p) {
   __shared__ double s_slot[kExprSlots * kBlock];
   __shared__ double s_temp[kExprTemps * kW * kBlock];
-  double *const sl = s_slot + threadIdx.x;
-  double *const tl = s_temp + threadIdx.x;
-  const int tile = blockIdx.x;
-  const int64_t block = blockIdx.y, slice = blockIdx.z;
-  const int64_t c = block * kBlock + threadIdx.x;
-  const bool live = c < p.n;
-  const int64_t cc = live ? c : p.n - 1;
-  const int64_t r0 = slice * p.slice_len;
-  const int64_t r1 = r0 + p.slice_len < p.count ? r0 + p.slice_len : p.count;
-  const int j0 = tile * kW;
+  const PointwiseGroup g = pointwise_group(p, blockIdx.x);
 
   LsePair lse[kW];
   Moments mom[kW];
@@ -77,83 +50,23 @@ __global__ __launch_bounds__(kBlock) void pointwise_kernel(KArgs a, PointwiseArg
     lse[i] = lse_identity();
     mom[i] = moments_identity();
   }
-  double x[D], xn[D];
-  load_draw(p, r0, cc, x);
-  for (int64_t r = r0; r < r1; ++r) {
-    load_draw(p, r + 1 < r1 ? r + 1 : r, cc, xn);
-    // the scalar prefix: the words before LOOP
-    double acc = 0.;
-    for (int pc = 0; pc < p.loop_pc; ++pc) {
-      const uint32_t w = __builtin_amdgcn_readfirstlane(cldw(a.ecode, pc));
-      const uint32_t op = expr_op(w);
-      const double va = expr_operand<D>(a, x, sl, acc, expr_a_kind(w), expr_a_idx(w));
-      double vb = 0.;
-      if (expr_binary(op)) vb = expr_operand<D>(a, x, sl, acc, expr_b_kind(w), expr_b_idx(w));
-      acc = expr_apply(op, va, vb);
-      if (expr_store(w)) sl[(expr_dst(w) & (kExprSlots - 1)) * kBlock] = acc;
-    }
-    double t[kW];
-    expr_body<D, kW>(a, x, sl, tl, p.loop_pc + 1, p.body_len, j0, t);
-    const double inv_n = 1. / (double)(r - r0 + 1);
+  pointwise_walk(a, p, g, s_slot + threadIdx.x, s_temp + threadIdx.x,
+                 [&](int64_t at, const double (&t)[kW]) {
+    const double inv_n = 1. / (double)(at + 1);
 #pragma unroll
     for (int i = 0; i < kW; ++i) {
       lse[i] = lse_push(lse[i], t[i]);
       mom[i] = moments_push(mom[i], t[i], inv_n);
     }
-#pragma unroll
-    for (int k = 0; k < D; ++k) x[k] = xn[k];
-  }
+  });
 
-  // the lanes' partials over the temporaries, [observation][m, s, mean, M2]
-  // [lane], and over the slots: the counts [lane], the 32 folded counts of each
-  // observation, then the shifts [observation][lane]
-  __syncthreads();
-  double *const s_n = s_slot, *const s_fn = s_slot + kBlock, *const s_k = s_slot + 2 * kBlock;
-  s_n[threadIdx.x] = live ? mom[0].n : 0.;
-#pragma unroll
-  for (int i = 0; i < kW; ++i) {
-    double *q = s_temp + (i * 4) * kBlock + threadIdx.x;
-    q[0 * kBlock] = live ? lse[i].m : -INFINITY;
-    q[1 * kBlock] = live ? lse[i].s : 0.;
-    q[2 * kBlock] = live ? mom[i].mean : 0.;
-    q[3 * kBlock] = live ? mom[i].m2 : 0.;
-    s_k[i * kBlock + threadIdx.x] = live ? mom[i].k : 0.;
-  }
-  __syncthreads();
-  const int o = threadIdx.x / kPointwiseFold, t = threadIdx.x % kPointwiseFold;
-  double *const q = s_temp + (o * 4) * kBlock, *const qk = s_k + o * kBlock;
-  double *const qn = s_fn + o * kPointwiseFold;
-  const auto lse_at = [&](int lane) { return LsePair{q[lane], q[kBlock + lane]}; };
-  const auto mom_at = [&](const double *n, int lane) {
-    return Moments{n[lane], qk[lane], q[2 * kBlock + lane], q[3 * kBlock + lane]};
-  };
-  LsePair fl = lse_at(t);
-  Moments fm = mom_at(s_n, t);
-  for (int lane = t + kPointwiseFold; lane < kBlock; lane += kPointwiseFold) {
-    fl = lse_merge(fl, lse_at(lane));
-    fm = moments_merge(fm, mom_at(s_n, lane));
-  }
-  // the 32 results of each observation go where its lanes 0..31 stood, then
-  // fold by halves
-  __syncthreads();
-  for (int w = kPointwiseFold; w > 0; w >>= 1) {
-    if (t < w) {
-      if (w < kPointwiseFold) {
-        fl = lse_merge(fl, lse_at(t + w));
-        fm = moments_merge(fm, mom_at(qn, t + w));
-      }
-      q[t] = fl.m;
-      q[kBlock + t] = fl.s;
-      q[2 * kBlock + t] = fm.mean;
-      q[3 * kBlock + t] = fm.m2;
-      qk[t] = fm.k;
-      qn[t] = fm.n;
-    }
-    __syncthreads();
-  }
+  LsePair fl;
+  Moments fm;
+  int o, t;
+  pointwise_merge_lanes(lse, mom, g.live, s_slot, s_temp, &fl, &fm, &o, &t);
   if (t == 0) {
-    const int64_t row = block * p.slices + slice, plane = p.rows * p.npad;
-    double *out = p.part + row * p.npad + j0 + o;
+    const int64_t row = g.block * p.slices + g.slice, plane = p.rows * p.npad;
+    double *out = p.part + row * p.npad + g.j0 + o;
     out[0 * plane] = fl.m;
     out[1 * plane] = fl.s;
     out[2 * plane] = fm.n;

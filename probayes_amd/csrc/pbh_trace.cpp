@@ -135,6 +135,35 @@ hipError_t launch_scores(pbh_engine *e, const pbh::RankLayout &l, int64_t k, int
   return err;
 }
 
+// The checks of a pointwise program that come before the window's, for `entry`:
+// a trace, the engine's dims, expr_check and the pointwise shape.  Fills prog
+// and loop_pc.
+int pointwise_program(pbh_engine *e, const char *entry, const int32_t *code, int32_t n_code,
+                      const double *consts, int32_t n_consts, int32_t depth, const double *data,
+                      int32_t n_cols, int32_t n_obs, pbh::ExprProgram *out, int *loop_pc) {
+  pbh::ExprProgram &prog = *out;
+  if (e->cap <= 0 || !e->tx)
+    return fail(PBH_ERR_STATE, "no trace allocated (pbh_alloc_trace first)");
+  if (e->d > PBH_EXPR_MAX_DIM)
+    return fail(PBH_ERR_ARG, "%s: the engine has %d dims, a program reads "
+                "at most %d variables", entry, (int)e->d, PBH_EXPR_MAX_DIM);
+  prog.d = (int32_t)e->d;
+  prog.code = code;
+  prog.n_code = n_code;
+  prog.consts = consts;
+  prog.n_consts = n_consts;
+  prog.depth = depth;
+  prog.data = data;
+  prog.n_cols = n_cols;
+  prog.n_obs = n_obs;
+  int pc = -1;
+  if (const char *bad = pbh::expr_check(prog, &pc))
+    return fail(PBH_ERR_ARG, "%s: bad program at word %d: %s", entry, pc, bad);
+  if (const char *bad = pbh::expr_pointwise_error(prog, loop_pc))
+    return fail(PBH_ERR_ARG, "%s: %s", entry, bad);
+  return PBH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -469,26 +498,8 @@ int pbh_trace_pointwise(pbh_engine *e, int64_t first, int64_t count, const int32
   pbh::ExprProgram prog;
   int loop_pc = -1;
   const auto own = [&] {
-    if (e->cap <= 0 || !e->tx)
-      return fail(PBH_ERR_STATE, "no trace allocated (pbh_alloc_trace first)");
-    if (e->d > PBH_EXPR_MAX_DIM)
-      return fail(PBH_ERR_ARG, "pbh_trace_pointwise: the engine has %d dims, a program reads "
-                  "at most %d variables", (int)e->d, PBH_EXPR_MAX_DIM);
-    prog.d = (int32_t)e->d;
-    prog.code = code;
-    prog.n_code = n_code;
-    prog.consts = consts;
-    prog.n_consts = n_consts;
-    prog.depth = depth;
-    prog.data = data;
-    prog.n_cols = n_cols;
-    prog.n_obs = n_obs;
-    int pc = -1;
-    if (const char *bad = pbh::expr_check(prog, &pc))
-      return fail(PBH_ERR_ARG, "pbh_trace_pointwise: bad program at word %d: %s", pc, bad);
-    if (const char *bad = pbh::expr_pointwise_error(prog, &loop_pc))
-      return fail(PBH_ERR_ARG, "pbh_trace_pointwise: %s", bad);
-    return PBH_OK;
+    return pointwise_program(e, "pbh_trace_pointwise", code, n_code, consts, n_consts, depth, data,
+                             n_cols, n_obs, &prog, &loop_pc);
   };
   if (const int rc = trace_enter(e, {{code, "code"}}, false, first, count, 1, own)) return rc;
   const int64_t n = e->n;
@@ -521,6 +532,145 @@ int pbh_trace_pointwise(pbh_engine *e, int64_t first, int64_t count, const int32
       err = hipMemcpy(outs[v], res + v * l.npad, (size_t)n_obs * sizeof(double),
                       hipMemcpyDeviceToHost);
   if (err != hipSuccess) return hip_fail("pbh_trace_pointwise", err);
+  return PBH_OK;
+}
+
+// The scratch is pointwise_layout's with tail_layout's words as the select
+// region.  The observations are taken in batches of tail_batch_tiles(capacity)
+// tiles, so that the candidate lists hold at most kTailListBytes (256 MiB)
+// whatever n_obs is, and the histograms at most 8 KB per observation of a
+// batch; a capacity above kTailMaxCapacity, whose one tile would not fit, is
+// refused.
+int pbh_trace_pointwise_tail(pbh_engine *e, int64_t first, int64_t count, const int32_t *code,
+                             int32_t n_code, const double *consts, int32_t n_consts,
+                             int32_t depth, const double *data, int32_t n_cols, int32_t n_obs,
+                             int64_t k, int64_t capacity, double *tail, double *rest_lse,
+                             int32_t *passes) {
+  constexpr char kEntry[] = "pbh_trace_pointwise_tail";
+  pbh::ExprProgram prog;
+  int loop_pc = -1;
+  const auto own = [&] {
+    if (!tail && !rest_lse)
+      return fail(PBH_ERR_ARG, "%s: tail and rest_lse are both NULL", kEntry);
+    return pointwise_program(e, kEntry, code, n_code, consts, n_consts, depth, data, n_cols, n_obs,
+                             &prog, &loop_pc);
+  };
+  if (const int rc = trace_enter(e, {{code, "code"}}, false, first, count, 1, own)) return rc;
+  const int64_t n = e->n, S = n * count;   // (the window lies in the trace: no overflow)
+  if (k < 1 || k >= S)
+    return fail(PBH_ERR_ARG, "%s: k = %lld outside 1 .. %lld, the draws less one", kEntry,
+                (long long)k, (long long)(S - 1));
+  if (capacity != 0 && capacity < k)
+    return fail(PBH_ERR_ARG, "%s: capacity = %lld below k = %lld", kEntry, (long long)capacity,
+                (long long)k);
+  if (capacity == 0) capacity = pbh::tail_default_capacity(k);
+  capacity = std::min(capacity, S);   // (no list holds more than every draw)
+  if (capacity > pbh::kTailMaxCapacity)
+    return fail(PBH_ERR_ARG, "%s: capacity = %lld above %lld, what one tile's lists may hold",
+                kEntry, (long long)capacity, (long long)pbh::kTailMaxCapacity);
+  std::vector<double> blk;
+  const pbh::ExprLayout el = pbh::expr_pack(blk, prog);
+  const int64_t tiles = ((int64_t)n_obs + pbh::kPointwiseTile - 1) / pbh::kPointwiseTile;
+  const int64_t batch = std::min(pbh::tail_batch_tiles(capacity), tiles);
+  const pbh::TailLayout tl = pbh::tail_layout(batch, capacity);
+  std::vector<pbh::PointwiseLayout> layouts;
+  size_t bytes = 0;
+  for (int64_t tile0 = 0; tile0 < tiles; tile0 += batch) {
+    const int64_t nb = std::min((int64_t)n_obs - tile0 * pbh::kPointwiseTile,
+                                batch * pbh::kPointwiseTile);
+    pbh::PointwiseLayout l;
+    if (!pbh::pointwise_layout(n, count, (int32_t)nb, tl.words, (int64_t)blk.size(), &l))
+      return fail(PBH_ERR_ARG, "%s: no scratch layout for %lld chains of %lld records", kEntry,
+                  (long long)n, (long long)count);
+    layouts.push_back(l);
+    bytes = std::max(bytes, (size_t)l.bytes);
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  if (const int rc = scratch(e, bytes)) return rc;
+  // (every batch has the same select and program regions)
+  double *dprog = at<double>(e->scratch, layouts[0].prog);
+  uint64_t *sel = at<uint64_t>(e->scratch, layouts[0].select);
+  // (blk and pfx are the sources of queued copies: the stream is synchronised
+  // after every launch and on the way out)
+  hipError_t err = hipMemcpyAsync(dprog, blk.data(), blk.size() * sizeof(double),
+                                  hipMemcpyHostToDevice, e->stream);
+  int32_t most = 0;
+  std::vector<uint64_t> pfx((size_t)tl.npad), hist, cursor, keys;
+  std::vector<double> part;
+  std::vector<pbh::LsePair> rows;
+  const char *broken = nullptr;
+  for (size_t b = 0; err == hipSuccess && !broken && b < layouts.size(); ++b) {
+    const pbh::PointwiseLayout &l = layouts[b];
+    const int64_t tile0 = (int64_t)b * batch, j0 = tile0 * pbh::kPointwiseTile;
+    const int64_t nb = std::min((int64_t)n_obs - j0, l.npad);
+    pbh::TailLaunch t{e->tx, n, first, count, (int32_t)e->d, loop_pc, n_obs, (int32_t)tile0,
+                      dprog, &el, e->scratch, &l, &tl, capacity};
+    std::vector<pbh::TailState> st((size_t)nb, pbh::TailState{0, (uint64_t)(k - 1), 0,
+                                                              (uint64_t)S});
+    std::fill(pfx.begin(), pfx.end(), 0);
+    const auto settled = [&] {
+      for (const pbh::TailState &s : st)
+        if (!pbh::tail_settled(s, capacity)) return false;
+      return true;
+    };
+    const auto put_prefixes = [&] {
+      for (int64_t j = 0; j < nb; ++j) pfx[(size_t)j] = st[(size_t)j].prefix;
+      return hipMemcpyAsync(sel + tl.prefix, pfx.data(), pfx.size() * 8, hipMemcpyHostToDevice,
+                            e->stream);
+    };
+    int32_t done = 0, ran = 0;
+    hist.resize((size_t)(nb * pbh::kTailBins));
+    while (err == hipSuccess && done < 64 && !settled()) {
+      err = put_prefixes();
+      if (err == hipSuccess) err = pbh::launch_tail_count(t, done, e->stream);
+      const hipError_t drained = hipStreamSynchronize(e->stream);
+      if (err == hipSuccess) err = drained;
+      if (err == hipSuccess)
+        err = hipMemcpy(hist.data(), sel + tl.hist, hist.size() * 8, hipMemcpyDeviceToHost);
+      if (err != hipSuccess) break;
+      const int bits = pbh::tail_digit_bits(done);
+      for (int64_t j = 0; j < nb; ++j)
+        pbh::tail_pick(hist.data() + j * pbh::kTailBins, bits, &st[(size_t)j]);
+      done += bits;
+      ++ran;
+    }
+    most = std::max(most, ran);
+    if (err == hipSuccess) err = put_prefixes();
+    if (err == hipSuccess) err = pbh::launch_tail_gather(t, done, e->stream);
+    const hipError_t drained = hipStreamSynchronize(e->stream);
+    if (err == hipSuccess) err = drained;
+    cursor.resize((size_t)nb);
+    part.resize((size_t)(2 * l.rows * l.npad));
+    rows.resize((size_t)l.rows);
+    if (err == hipSuccess)
+      err = hipMemcpy(cursor.data(), sel + tl.cursor, cursor.size() * 8, hipMemcpyDeviceToHost);
+    if (err == hipSuccess)
+      err = hipMemcpy(part.data(), at<const double>(e->scratch, l.part), part.size() * 8,
+                      hipMemcpyDeviceToHost);
+    for (int64_t j = 0; err == hipSuccess && j < nb; ++j) {
+      const pbh::TailState &s = st[(size_t)j];
+      if (cursor[(size_t)j] != pbh::tail_candidates(s, done) ||
+          cursor[(size_t)j] > (uint64_t)capacity) {
+        broken = "the candidates gathered are not those counted";
+        break;
+      }
+      keys.resize((size_t)cursor[(size_t)j]);
+      if (!keys.empty())
+        err = hipMemcpy(keys.data(), sel + tl.list + j * capacity, keys.size() * 8,
+                        hipMemcpyDeviceToHost);
+      if (err != hipSuccess) break;
+      for (int64_t r = 0; r < l.rows; ++r)
+        rows[(size_t)r] = pbh::LsePair{part[(size_t)(r * l.npad + j)],
+                                       part[(size_t)((l.rows + r) * l.npad + j)]};
+      pbh::tail_finish(keys.data(), (int64_t)keys.size(), k, done, s, rows.data(), l.rows,
+                       tail ? tail + (j0 + j) * k : nullptr,
+                       rest_lse ? rest_lse + j0 + j : nullptr);
+    }
+  }
+  (void)hipStreamSynchronize(e->stream);
+  if (err != hipSuccess) return hip_fail(kEntry, err);
+  if (broken) return fail(PBH_ERR_HIP, "%s: %s", kEntry, broken);
+  if (passes) *passes = most;
   return PBH_OK;
 }
 

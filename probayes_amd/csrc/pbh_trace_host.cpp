@@ -2,6 +2,7 @@
 #include "pbh_trace_host.h"
 
 #include <stdio.h>
+#include <string.h>
 
 #include <algorithm>
 #include <cmath>
@@ -241,6 +242,71 @@ void pointwise_finish(const LsePair *lse, const Moments *mom, int64_t rows, doub
   if (lse_out) *lse_out = lse_value(l);
   if (mean_out) *mean_out = moments_mean(m);
   if (var_out) *var_out = m.m2 / (m.n - 1.);
+}
+
+uint64_t tail_key(double v) {
+  if (v != v) return ~0ull;
+  if (v == 0.) v = 0.;
+  uint64_t u;
+  memcpy(&u, &v, 8);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+double tail_key_value(uint64_t key) {
+  if (key == ~0ull) return std::numeric_limits<double>::quiet_NaN();
+  const uint64_t u = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
+  double v;
+  memcpy(&v, &u, 8);
+  return v;
+}
+
+void tail_pick(const uint64_t *hist, int bits, TailState *s) {
+  const uint64_t bins = (uint64_t)1 << bits;
+  uint64_t before = 0, digit = 0;
+  for (; digit + 1 < bins && before + hist[digit] <= s->rank; ++digit) before += hist[digit];
+  s->prefix = (s->prefix << bits) | digit;
+  s->rank -= before;
+  s->below += before;
+  s->under = hist[digit];
+}
+
+void tail_finish(uint64_t *keys, int64_t n_keys, int64_t k, int done, const TailState &s,
+                 const LsePair *rows, int64_t n_rows, double *tail, double *rest_lse) {
+  std::sort(keys, keys + n_keys);
+  const double cut = tail_key_value(s.prefix);   // (read with all 64 bits fixed only)
+  if (tail)
+    for (int64_t i = 0; i < k; ++i) tail[i] = i < n_keys ? tail_key_value(keys[i]) : cut;
+  if (!rest_lse) return;
+  LsePair rest = lse_identity();
+  for (int64_t i = k; i < n_keys; ++i) rest = lse_push(rest, -tail_key_value(keys[i]));
+  if (done == 64) {
+    // of the `under` keys at the cut, rank + 1 went into the tail
+    const uint64_t ties = s.under - (s.rank + 1);
+    if (ties) rest = lse_merge(rest, LsePair{-cut, (double)ties});
+  }
+  LsePair dev = lse_identity();
+  for (int64_t r = 0; r < n_rows; ++r) dev = lse_merge(dev, rows[r]);
+  *rest_lse = lse_value(lse_merge(rest, dev));
+}
+
+int64_t tail_default_capacity(int64_t k) {
+  return k > 32768 ? 2 * k : 65536;
+}
+
+int64_t tail_batch_tiles(int64_t capacity) {
+  const int64_t tiles = kTailListBytes / (capacity * 8 * kPointwiseTile);
+  return tiles < 1 ? 1 : tiles;
+}
+
+TailLayout tail_layout(int64_t tiles, int64_t capacity) {
+  TailLayout l;
+  l.npad = tiles * kPointwiseTile;
+  l.prefix = 0;
+  l.cursor = l.npad;
+  l.hist = 2 * l.npad;
+  l.list = l.hist + l.npad * kTailBins;
+  l.words = l.list + l.npad * capacity;
+  return l;
 }
 
 }  // namespace pbh

@@ -2,7 +2,9 @@
 // check every trace entry point makes, the checks of a quantile list, and the
 // host steps of the pooled quantile around the device's radix select, and the
 // geometry and scratch layout of the pooled sort (pbh_rank.hip), and the layout
-// and the estimator of the ESS across chains (pbh_ess_rank.hip).  No HIP: a host
+// and the estimator of the ESS across chains (pbh_ess_rank.hip), the layout and
+// the merges of the pointwise reduction (pbh_pointwise.hip), and the pick and
+// the finish of its tail select (pbh_pointwise_tail.hip).  No HIP: a host
 // compiler alone builds it (tests/trace_host_main.cpp, the one program the CPU
 // tests drive it through).  Built with -ffp-contract=off: the interpolation and
 // the estimator must round as NumPy's do.
@@ -127,5 +129,69 @@ void pointwise_combine(const LsePair *lse, const Moments *mom, LsePair *lse_out,
 // then lse, mean and the variance at ddof 1 (any of the three may be null).
 void pointwise_finish(const LsePair *lse, const Moments *mom, int64_t rows, double *lse_out,
                       double *mean_out, double *var_out);
+
+// The tail of the pointwise terms (pbh_pointwise_tail.hip): per observation the
+// k smallest terms over the S = n count draws of a window and the log-sum-exp
+// of minus the others, by a most-significant-digit radix select on tail_key,
+// the monotone 64-bit image of a double (pbh_device.h key_image: negative
+// values reversed below the positive ones, either zero one image, every NaN
+// the largest).  The digits are kTailDigit = 10 bits wide, the seventh the 4
+// bits that remain.  The device counts and gathers; the host picks and
+// finishes:
+//   tail_pick    after a count pass over the keys under the observation's
+//       prefix: the digit at which the running count first exceeds the
+//       remaining rank is appended to the prefix.
+//   tail_settled whether the keys at or under the prefix -- below + under of
+//       them -- fit a candidate list of `capacity`; the passes stop when every
+//       observation is settled or all 64 bits are fixed.
+//   tail_finish  the candidates the device gathered (keys whose prefix is <=
+//       the observation's; with all 64 bits fixed only the keys below the cut,
+//       the `under` keys equal to it being neither gathered nor folded),
+//       sorted; the first k are the tail, filled up with the cut; what remains
+//       is pushed in ascending order into a log-sum-exp pair of the negated
+//       values (remaining ties as one pair (-v, count)) and merged with the
+//       device's partial rows in index order.
+constexpr int kTailDigit = 10, kTailBins = 1 << kTailDigit;
+inline int tail_digit_bits(int done) { return 64 - done < kTailDigit ? 64 - done : kTailDigit; }
+uint64_t tail_key(double v);
+double tail_key_value(uint64_t key);   // +0.0 for either zero, one quiet NaN for every NaN
+// prefix: the `done` bits fixed so far, right-aligned; rank: the rank that
+// remains among the `under` keys under the prefix; below: the keys whose
+// prefix is smaller.  Start: (0, k - 1, 0, S).
+struct TailState {
+  uint64_t prefix, rank, below, under;
+};
+// hist [1 << bits]: the counts of the next digit among the keys under s.prefix
+// (their sum is s.under, rank < under).
+void tail_pick(const uint64_t *hist, int bits, TailState *s);
+inline bool tail_settled(const TailState &s, int64_t capacity) {
+  return s.below + s.under <= (uint64_t)capacity;
+}
+// How many candidates the device gathers for s after `done` bits.
+inline uint64_t tail_candidates(const TailState &s, int done) {
+  return done == 64 ? s.below : s.below + s.under;
+}
+// keys [n_keys]: the gathered candidates in any order (sorted in place), n_keys
+// = tail_candidates(s, done) >= k, or with done == 64 >= k - s.under.  rows
+// [n_rows]: the device's partial pairs of the other terms, negated.  tail [k]
+// and rest_lse may be null.
+void tail_finish(uint64_t *keys, int64_t n_keys, int64_t k, int done, const TailState &s,
+                 const LsePair *rows, int64_t n_rows, double *tail, double *rest_lse);
+
+// The select's scratch of one batch of `tiles` observation tiles, in 8-byte
+// words from the start of the reduction scratch (pointwise_layout's select
+// region): prefix [npad], cursor [npad], hist [npad][kTailBins], list [npad]
+// [capacity], npad = 8 tiles.  The lists are held to kTailListBytes whatever
+// n_obs is: tail_batch_tiles is how many tiles a batch may hold, at least 1 --
+// capacity <= kTailMaxCapacity = kTailListBytes / 64 makes one tile fit.
+constexpr int64_t kTailListBytes = (int64_t)256 << 20;
+constexpr int64_t kTailMaxCapacity = kTailListBytes / (8 * kPointwiseTile);
+struct TailLayout {
+  int64_t npad, prefix, cursor, hist, list, words;
+};
+int64_t tail_batch_tiles(int64_t capacity);
+TailLayout tail_layout(int64_t tiles, int64_t capacity);
+// max(2 k, 65 536)
+int64_t tail_default_capacity(int64_t k);
 
 }  // namespace pbh

@@ -30,6 +30,14 @@ pointwise_stats and waic are the definition of the pointwise log-likelihood
 reduction (pbh_trace_pointwise, Engine.trace_pointwise): per observation the
 log-sum-exp, the mean and the variance over the draws of its term, and lppd,
 p_waic and WAIC from those (Watanabe 2010; Vehtari, Gelman & Gabry 2017).
+
+pointwise_tail, gpd_fit, psis_loo_from_tail and psis_loo are the definition of
+PSIS-LOO, leave-one-out by Pareto-smoothed importance sampling (Vehtari,
+Gelman & Gabry 2017; Vehtari et al. 2024; the generalised-Pareto fit is Zhang &
+Stephens 2009): per observation the smallest terms and the log-sum-exp of the
+rest (pbh_trace_pointwise_tail, Engine.trace_pointwise_tail), and elpd_loo and
+the Pareto shape from those.  compare_elpd is the difference of two models'
+pointwise rows, WAIC's or LOO's, with its standard error.
 """
 import math
 
@@ -476,3 +484,161 @@ def waic(lse, mean, var, S):
             'lppd': float(lppd_i.sum()), 'p_waic': float(p_waic_i.sum()),
             'elpd_waic': elpd, 'se': float(np.sqrt(lse.size * np.var(elpd_i))),
             'waic': -2. * elpd}
+
+
+def pointwise_tail(T, k):
+  """(tail [n, k], rest_lse [n]) of the terms T [S, n], 1 <= k < S: per
+  observation j the k smallest terms, ascending, and log sum exp(-T[s, j]) over
+  the other S - k draws.  The order is that of the terms' 64-bit images: either
+  zero is +0.0, and NaN, one quiet NaN for every payload, comes last, so a tail
+  holds a NaN only when fewer than k terms are not NaN.  rest_lse has
+  pointwise_stats' conventions: shifted by the maximum, taken as 0 when that is
+  not finite, so -inf when every other term is +inf, +inf with a -inf among
+  them, NaN with a NaN."""
+  T = np.asarray(T, float)
+  k = int(k)
+  if T.ndim != 2 or not 1 <= k < T.shape[0]:
+    raise ValueError('pointwise_tail: terms [S, n] and 1 <= k < S, got shape {} and k = {}'
+                     .format(T.shape, k))
+  with np.errstate(all='ignore'):
+    t = np.sort(np.where(np.isnan(T), np.nan, T + 0.), axis=0)
+    rest = -t[k:]
+    top = rest.max(axis=0)
+    top = np.where(np.isfinite(top), top, 0.)
+    rest_lse = np.log(np.exp(rest - top).sum(axis=0)) + top
+  return np.ascontiguousarray(t[:k].T), rest_lse
+
+
+def gpd_fit(x):
+  """(k, sigma) of the generalised Pareto distribution fitted to the ascending
+  sample x >= 0, x[-1] > 0, of m exceedances: Zhang & Stephens' (2009)
+  estimator, the posterior mean of theta = -k / sigma under their data-
+  dependent prior on a grid of 30 + floor(sqrt(m)) points theta_j = 1 / x_m + (1
+  - sqrt(M / (j - 1/2))) / (3 x*), x* the first-quartile element x[floor(m / 4
+  + 1/2) - 1], weighted by the profile likelihood L(theta) = m (log(-theta /
+  k(theta)) - k(theta) - 1), k(theta) = mean log1p(-theta x); then k at the
+  mean theta, sigma = -k / theta, and k drawn towards 1/2 by the weakly
+  informative prior of Vehtari et al. (2024), k <- (m k + 5) / (m + 10).
+  x -> c x leaves k and sigma / c unchanged."""
+  x = np.asarray(x, float)
+  m = x.size
+  M = 30 + int(math.floor(math.sqrt(m)))
+  xstar = x[int(math.floor(m / 4. + 0.5)) - 1]
+  j = np.arange(1, M + 1, dtype=float)
+  theta = 1. / x[-1] + (1. - np.sqrt(M / (j - 0.5))) / (3. * xstar)
+  kj = np.log1p(-theta[:, None] * x[None, :]).mean(axis=1)
+  L = m * (np.log(-theta / kj) - kj - 1.)
+  with np.errstate(over='ignore'):    # (a point far below the best weighs 1 / inf = 0)
+    w = 1. / np.exp(L[None, :] - L[:, None]).sum(axis=1)
+  th = float((theta * w).sum())
+  k = float(np.log1p(-th * x).mean())
+  sigma = -k / th
+  return (m * k + 5.) / (m + 10.), sigma
+
+
+def psis_tail_length(S):
+  """m = min(floor(S / 5), ceil(3 sqrt(S))), the draws PSIS smooths; m >= 5, so
+  S >= 25, or ValueError."""
+  S = int(S)
+  m = min(S // 5, int(math.ceil(3. * math.sqrt(S)))) if S > 0 else 0
+  if m < 5:
+    raise ValueError('psis: S = {} draws leave a tail of {}: at least 5, S >= 25'.format(S, m))
+  return m
+
+
+def _lse(v):
+  """log sum exp of a vector, pointwise_stats' conventions"""
+  top = v.max()
+  top = top if np.isfinite(top) else 0.
+  return float(np.log(np.exp(v - top).sum()) + top)
+
+
+def psis_loo_from_tail(tail, rest_lse, S, lse=None):
+  """PSIS-LOO per observation from pointwise_tail(T, m + 1) of its S draws, m =
+  psis_tail_length(S): {'elpd_loo_i': [n], 'pareto_k': [n]}.  Write a sorted
+  tail t_0 <= .. <= t_m.  The importance log-ratios are -T: the cutoff is -t_m,
+  the m tail ratios lw_i = -t_i, i < m, all shifted by -t_0 so that the largest
+  is 0.  gpd_fit on exp(lw) - exp(cutoff), ascending, gives (k, sigma); the r-th
+  smallest tail ratio is replaced by log(sigma expm1(-k log1p(-p_r)) / k +
+  exp(cutoff)), p_r = (r - 1/2) / m, truncated at the raw maximum.  log sum w
+  is the log-sum-exp of rest_lse, the cutoff and the smoothed ratios; sum w p =
+  (S - m) + sum_r exp(smoothed_r + t_(r)), a draw outside the tail giving
+  exactly 1; elpd_loo_i = log sum w p - log sum w, pareto_k = k.
+  One rule for the degenerate rows.  A NaN in the tail or in rest_lse makes the
+  row NaN, both values.  Otherwise an infinite term in the tail, an infinite
+  rest_lse, or a zero at the fit's first-quartile element (the tail is tied
+  with the cutoff that far) gives pareto_k = +inf and no smoothing: elpd_loo_i
+  = log S - log sum w over the raw ratios.
+  With lse [n], pointwise_stats' log-sum-exp of the same terms, the summary is
+  added: 'p_loo_i' = lppd_i - elpd_loo_i with lppd_i = lse - log S; 'elpd_loo'
+  and 'p_loo', the sums; 'se' = sqrt(n var(elpd_loo_i)) (np.var, ddof 0);
+  'looic' = -2 elpd_loo; 'n_bad_k', the observations whose pareto_k is not <=
+  min(1 - 1 / log10(S), 0.7), where neither estimate can be trusted."""
+  tail, rest_lse = np.asarray(tail, float), np.asarray(rest_lse, float)
+  S = int(S)
+  m = psis_tail_length(S)
+  if tail.ndim != 2 or tail.shape[1] != m + 1 or rest_lse.shape != tail.shape[:1]:
+    raise ValueError('psis_loo_from_tail: tail [n, {}] and rest_lse [n] for S = {}, got {} and {}'
+                     .format(m + 1, S, tail.shape, rest_lse.shape))
+  n = tail.shape[0]
+  elpd, khat = np.empty(n), np.empty(n)
+  p = (np.arange(1, m + 1) - 0.5) / m
+  quartile = int(math.floor(m / 4. + 0.5)) - 1
+  with np.errstate(all='ignore'):
+    for j in range(n):
+      t, rest = tail[j], float(rest_lse[j])
+      if np.isnan(t).any() or np.isnan(rest):
+        elpd[j] = khat[j] = np.nan
+        continue
+      shift = t[0]
+      lw = (shift - t[:m])[::-1]          # ascending, the largest 0
+      cut = shift - t[m]
+      x = np.exp(lw) - np.exp(cut)
+      if not (np.isfinite(t).all() and np.isfinite(rest)) or not x[quartile] > 0.:
+        khat[j] = np.inf
+        elpd[j] = math.log(S) - _lse(np.concatenate(([rest], -t)))
+        continue
+      k, sigma = gpd_fit(x)
+      q = -np.log1p(-p) * sigma if k == 0. else sigma * np.expm1(-k * np.log1p(-p)) / k
+      smooth = np.minimum(np.log(q + np.exp(cut)), 0.)
+      log_sum_w = _lse(np.concatenate(([rest, -t[m]], smooth - shift)))
+      sum_wp = (S - m) + float(np.exp((smooth - shift) + t[:m][::-1]).sum())
+      khat[j] = k
+      elpd[j] = math.log(sum_wp) - log_sum_w
+    res = {'elpd_loo_i': elpd, 'pareto_k': khat}
+    if lse is not None:
+      lppd_i = np.asarray(lse, float) - math.log(S)
+      total = float(elpd.sum())
+      bad = min(1. - 1. / math.log10(S), 0.7)
+      res.update({'p_loo_i': lppd_i - elpd, 'elpd_loo': total,
+                  'p_loo': float((lppd_i - elpd).sum()),
+                  'se': float(np.sqrt(n * np.var(elpd))), 'looic': -2. * total,
+                  'n_bad_k': int(np.count_nonzero(~(khat <= bad)))})
+  return res
+
+
+def psis_loo(T):
+  """PSIS-LOO of the terms T [S, n], the pointwise log-likelihood of S draws:
+  pointwise_tail(T, m + 1), then psis_loo_from_tail with pointwise_stats' lse --
+  the rows 'elpd_loo_i', 'pareto_k', 'p_loo_i' and 'elpd_loo', 'p_loo', 'se',
+  'looic', 'n_bad_k'."""
+  T = np.asarray(T, float)
+  if T.ndim != 2:
+    raise ValueError('psis_loo: terms [S, n], got shape {}'.format(T.shape))
+  S = T.shape[0]
+  tail, rest_lse = pointwise_tail(T, psis_tail_length(S) + 1)
+  with np.errstate(all='ignore'):
+    lse = pointwise_stats(T)[0]
+  return psis_loo_from_tail(tail, rest_lse, S, lse)
+
+
+def compare_elpd(a_i, b_i):
+  """(elpd_diff, se) of two models on the same n observations from their
+  pointwise elpd rows, waic's 'elpd_i' or psis_loo's 'elpd_loo_i': the sum of
+  a_i - b_i -- positive where a predicts better -- and sqrt(n var(a_i - b_i))
+  (np.var, ddof 0), the standard error of that sum."""
+  a_i, b_i = np.asarray(a_i, float), np.asarray(b_i, float)
+  if a_i.ndim != 1 or a_i.shape != b_i.shape:
+    raise ValueError('compare_elpd: two rows [n], got {} and {}'.format(a_i.shape, b_i.shape))
+  diff = a_i - b_i
+  return float(diff.sum()), float(np.sqrt(diff.size * np.var(diff)))

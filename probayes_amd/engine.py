@@ -767,6 +767,15 @@ class Engine:
     order; it has nothing to do with the engine's own model, which may be of
     any kind.  N count >= 2."""
     first, count = self._window(first, count)
+    args, n_obs = self._pointwise_args(program, first, count)
+    out = np.empty((3, max(n_obs, 1)))
+    _lib.call('pbh_trace_pointwise', *args, _dp(out[0]), _dp(out[1]), _dp(out[2]))
+    return {'lse': out[0].copy(), 'mean': out[1].copy(), 'var': out[2].copy()}
+
+  def _pointwise_args(self, program, first, count):
+    """The engine, window and program arguments pbh_trace_pointwise and
+    pbh_trace_pointwise_tail share (each pointer keeps its array alive), and
+    n_obs."""
     code = np.ascontiguousarray(program['code'], dtype=np.int32)
     consts = _f64(program['consts']).ravel()
     if consts.size == 0:
@@ -774,14 +783,31 @@ class Engine:
     data = program.get('data')
     data = None if data is None else np.atleast_2d(_f64(data))
     n_cols, n_obs = (0, 0) if data is None else data.shape
-    out = np.empty((3, max(int(n_obs), 1)))
-    _lib.call('pbh_trace_pointwise', self._h, _c.c_int64(int(first)),
-              _c.c_int64(int(count)), _ip(code), _c.c_int32(code.size), _dp(consts),
-              _c.c_int32(np.asarray(program['consts']).size),
-              _c.c_int32(int(program['depth'])), None if data is None else _dp(data),
-              _c.c_int32(int(n_cols)), _c.c_int32(int(n_obs)),
-              _dp(out[0]), _dp(out[1]), _dp(out[2]))
-    return {'lse': out[0].copy(), 'mean': out[1].copy(), 'var': out[2].copy()}
+    args = (self._h, _c.c_int64(int(first)), _c.c_int64(int(count)), _ip(code),
+            _c.c_int32(code.size), _dp(consts),
+            _c.c_int32(np.asarray(program['consts']).size),
+            _c.c_int32(int(program['depth'])), None if data is None else _dp(data),
+            _c.c_int32(int(n_cols)), _c.c_int32(int(n_obs)))
+    return args, int(n_obs)
+
+  def trace_pointwise_tail(self, program, k, first=0, count=None, capacity=0):
+    """Per observation, the k smallest of the terms a pointwise program gives
+    over the S = N count draws of trace records [first, first + count) and the
+    log-sum-exp of minus the other S - k, computed on the device without the
+    terms ever being stored (expr.evaluate_pointwise and diag.pointwise_tail are
+    the definition): {'tail': [n_obs, k] ascending (either zero as +0.0, NaN
+    last), 'rest_lse': [n_obs], 'passes': the count passes of the radix select}
+    -- what diag.psis_loo_from_tail needs with k = m + 1.  capacity: the
+    candidates kept per observation for the host's sort (0: max(2 k, 65 536));
+    the select passes until they fit.  1 <= k < S, capacity >= k."""
+    first, count = self._window(first, count)
+    args, n_obs = self._pointwise_args(program, first, count)
+    k = int(k)
+    tail, rest = np.empty((max(n_obs, 1), max(k, 1))), np.empty(max(n_obs, 1))
+    passes = _c.c_int32(0)
+    _lib.call('pbh_trace_pointwise_tail', *args, _c.c_int64(k), _c.c_int64(int(capacity)),
+              _dp(tail), _dp(rest), _c.byref(passes))
+    return {'tail': tail, 'rest_lse': rest, 'passes': int(passes.value)}
 
   def rccl_allreduce_max(self, value):
     v = _c.c_double(float(value))

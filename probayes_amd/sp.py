@@ -1476,6 +1476,25 @@ class Sampler:
     res = self.trace_pointwise(fn, first, count)
     return diag.waic(res['lse'], res['mean'], res['var'], self._eng.n * count)
 
+  def trace_loo(self, fn, first=0, count=None):
+    """PSIS-LOO of the pointwise log-likelihood fn over every chain and every
+    record [first, first + count): with S = N count draws and m = min(S // 5,
+    ceil(3 sqrt(S))), the m + 1 smallest terms of every observation and the
+    log-sum-exp of the rest from the device trace (Engine.
+    trace_pointwise_tail), lse from Engine.trace_pointwise, then diag.
+    psis_loo_from_tail: {'elpd_loo', 'p_loo', 'se', 'looic', 'n_bad_k'} and the
+    per-observation rows 'elpd_loo_i', 'pareto_k', 'p_loo_i'.  A pareto_k above
+    min(1 - 1 / log10(S), 0.7) says that neither this estimate nor trace_waic's
+    can be trusted for that observation.  S >= 25."""
+    from probayes_amd import diag, expr
+    first, count = self._device_window('trace_loo', first, count)
+    S = self._eng.n * count
+    m = diag.psis_tail_length(S)
+    program = expr.trace_pointwise(fn, self.names)
+    tail = self._eng.trace_pointwise_tail(program, m + 1, first, count)
+    lse = self._eng.trace_pointwise(program, first, count)['lse']
+    return diag.psis_loo_from_tail(tail['tail'], tail['rest_lse'], S, lse)
+
   def trace_quantile_pooled(self, q, first=0, count=None):
     """The posterior quantiles q of every name, pooled over every chain and
     every record [first, first + count), computed by the engine from its
