@@ -671,6 +671,31 @@ int pbh_trace_pointwise_tail(pbh_engine *eng, int64_t first, int64_t count,
                              int32_t n_obs, int64_t k, int64_t capacity,
                              double *tail, double *rest_lse, int32_t *passes);
 
+/* Posterior covariance over trace records [first, first + count) on the
+ * device, pooled over every chain and record (added within revision 2 as
+ * pbh_trace_rhat was: PBH_ABI_REVISION did not change for it, look the symbol
+ * up).  probayes_amd/diag.py pooled_cov is the definition.  With M = N count
+ * draws, K [d] the mean over chains of record `first` and v = x - K: S_a = sum
+ * v_a and P_ab = sum v_a v_b over the window;
+ * mean [d]: K + S / M.
+ * cov [d][d]: (P_ab - S_a S_b / M) / (M - 1), computed for a <= b and
+ * mirrored, so the matrix is symmetric in its bits.
+ * corr [d][d]: cov_ab / sqrt(cov_aa cov_bb), the diagonal included.
+ * The shift costs no traffic and lies among the draws, so S S / M cancels
+ * against P only mildly wherever the posterior lies; sums of raw products lose
+ * everything once the mean is large against the spread.
+ * Each of the three may be NULL; with all three NULL the call returns
+ * PBH_ERR_ARG (whatever else it was given).  The values are the IEEE results
+ * of the formulas with no special cases: chains that are constant and equal
+ * give cov exactly 0 and corr NaN (0 / 0), also on the diagonal, which is
+ * exactly 1 otherwise; a NaN record propagates.  The products are accumulated
+ * with a fused multiply-add, so the definition is met to rounding, not bit for
+ * bit.  Sums run in a fixed order without atomics: two calls on one trace give
+ * the same bits.  count >= 1 and N count >= 2.  Changes nothing in the engine:
+ * not the moments, the ESS, the trace, the chains or the generators.         */
+int pbh_trace_cov(pbh_engine *eng, int64_t first, int64_t count, double *mean,
+                  double *cov, double *corr);
+
 /* ---- multi-GPU: one RCCL all-gather over xGMI --------- */
 int pbh_rccl_unique_id(uint8_t id[128]);
 int pbh_rccl_init(pbh_engine *eng, int32_t rank, int32_t world,

@@ -183,6 +183,9 @@ SIGNATURES = {
                                                 ctypes.c_int32, ctypes.c_int32,
                                                 ctypes.c_int64, ctypes.c_int64, _dp, _dp,
                                                 _i32p]),
+    # (likewise within revision 2)
+    'pbh_trace_cov': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
+                                     ctypes.c_int64, _dp, _dp, _dp]),
     'pbh_trace_ess':(ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
                                      ctypes.c_int64, _dp]),
     'pbh_rccl_allreduce_max': (ctypes.c_int, [ctypes.c_void_p, _dp]),

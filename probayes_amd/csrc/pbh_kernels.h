@@ -345,6 +345,14 @@ struct TailLaunch {
 };
 hipError_t launch_tail_count(const TailLaunch &t, int32_t done, hipStream_t s);
 hipError_t launch_tail_gather(const TailLaunch &t, int32_t done, hipStream_t s);
+// The pooled covariance of trace records [first, first + count) (pbh_cov.hip),
+// count >= 1, d <= PBH_MAX_DIM.  l: cov_layout's partition and offsets into
+// scratch (pbh_trace_host.h).  Leaves K [d] at scratch + l.K and S [d], then
+// P's packed upper triangle, at scratch + l.res -- what cov_finish takes.  A
+// fixed reduction order, no atomics.
+struct CovLayout;
+hipError_t launch_cov(const double *tx, int64_t n, int32_t d, int64_t first, int64_t count,
+                      unsigned char *scratch, const CovLayout &l, hipStream_t s);
 // fft: 2 = the 2 048-point FFT form for count <= 1 536 records with the
 // 4 096-point form for the pairs it cannot decide (list: (d n + 1) / 2 + 1
 // int32 of device scratch), 1 = the 4 096-point form for count <= 2 048

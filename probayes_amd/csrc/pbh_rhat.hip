@@ -23,8 +23,8 @@
 //   cross chain over the small stats arrays, two passes each (the mean first,
 //               then the squared deviations from it; never sum m^2 - (sum m)^2
 //               / n), every element assigned to a fixed thread and the partial
-//               sums combined by a fixed tree in LDS: no atomics, the same bits
-//               every call.
+//               sums combined by a fixed tree in LDS (pbh_reduce_impl.h): no
+//               atomics, the same bits every call.
 //               rhat_group_thread_kernel / rhat_group_block_kernel reduce each
 //               superchain of `group` consecutive chains to (mu_k, B_k + W_k):
 //               a thread per superchain up to kThreadGroup chains, a workgroup
@@ -39,6 +39,7 @@
 #include <stdint.h>
 
 #include "pbh_kernels.h"
+#include "pbh_reduce_impl.h"
 
 namespace pbh {
 namespace {
@@ -47,7 +48,6 @@ constexpr int kUnroll = 8;          // records in flight per lane
 constexpr int kThreadGroup = 32;    // superchains of at most this many chains: one thread each
 constexpr int kGroupT = 256;        // workgroup of a superchain of up to kGroupWide chains,
 constexpr int kGroupWide = 2048;    // kFinalT threads above
-constexpr int kBatch = 16;          // loads in flight per thread of the cross-chain sums
 constexpr int kFinalT = 1024;       // workgroup of the final reduction
 
 // Adds records p[0], p[stride], ... (nrec of them) shifted by K to (s, q) and
@@ -110,43 +110,6 @@ __global__ __launch_bounds__(256) void rhat_chain_kernel(const double *__restric
   stats[3 * row + at] = shifted_var(s2, q2, nh);
   stats[4 * row + at] = K + sw / nw;
   stats[5 * row + at] = shifted_var(sw, qw, nw);
-}
-
-// Sums part[0..T) into part[0] by a fixed tree; every thread of the workgroup
-// calls it, and all read the total.
-template <int T>
-__device__ __forceinline__ double tree_sum(double *part, double mine) {
-  __syncthreads();   // the previous total has been read
-  part[threadIdx.x] = mine;
-  __syncthreads();
-#pragma unroll
-  for (int w = T / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-    __syncthreads();
-  }
-  return part[0];
-}
-
-// Thread t's share of sum_j term(load(j)) over j = t, t + T, ... < L, added in
-// that order.  kBatch values are loaded before any is used -- the loads are
-// independent, so they are in flight together (a thread of the final
-// reduction has 128 elements at 65 536 chains: one load per round trip made
-// that kernel 0.11 ms).  A batch that reaches past L loads element L - 1
-// again and adds +0 in its place.
-template <int T, class Load, class Term>
-__device__ __forceinline__ double strided_sum(int64_t L, Load load, Term term) {
-  double acc = 0.;
-  for (int64_t j = threadIdx.x; j < L; j += (int64_t)kBatch * T) {
-    double x[kBatch];
-#pragma unroll
-    for (int i = 0; i < kBatch; ++i) {
-      const int64_t at = j + (int64_t)i * T;
-      x[i] = load(at < L ? at : L - 1);
-    }
-#pragma unroll
-    for (int i = 0; i < kBatch; ++i) acc += j + (int64_t)i * T < L ? term(x[i]) : 0.;
-  }
-  return acc;
 }
 
 // Superchains of m <= kThreadGroup chains: thread (k, g) reduces superchain g

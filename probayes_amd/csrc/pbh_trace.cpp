@@ -302,6 +302,38 @@ int pbh_trace_rhat(pbh_engine *e, int64_t first, int64_t count, int32_t group,
   return PBH_OK;
 }
 
+int pbh_trace_cov(pbh_engine *e, int64_t first, int64_t count, double *mean, double *cov,
+                  double *corr) {
+  if (!mean && !cov && !corr)
+    return fail(PBH_ERR_ARG, "pbh_trace_cov: no output asked for (mean, cov and corr are all "
+                "NULL)");
+  if (const int rc = trace_enter(e, {}, true, first, count, 1)) return rc;
+  const int64_t n = e->n, d = e->d;
+  if (n < 2 && count < 2)
+    return fail(PBH_ERR_ARG, "pbh_trace_cov: %lld chain of %lld record: a covariance needs at "
+                "least 2 draws", (long long)n, (long long)count);
+  pbh::CovLayout l;
+  if (!pbh::cov_layout(n, count, (int32_t)d, &l))
+    return fail(PBH_ERR_ARG, "pbh_trace_cov: no scratch layout for %lld chains of %lld records "
+                "of %lld dims", (long long)n, (long long)count, (long long)d);
+  HIP_TRY(hipSetDevice(e->device));
+  if (const int rc = scratch(e, (size_t)l.bytes)) return rc;
+  hipError_t err = pbh::launch_cov(e->tx, n, (int32_t)d, first, count, e->scratch, l, e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  // the shift and the merged sums (S, then P's packed triangle), then the last
+  // step on the host
+  double K[PBH_MAX_DIM], sums[PBH_MAX_DIM + PBH_MAX_DIM * (PBH_MAX_DIM + 1) / 2];
+  if (err == hipSuccess)
+    err = hipMemcpy(K, at<const double>(e->scratch, l.K), (size_t)d * sizeof(double),
+                    hipMemcpyDeviceToHost);
+  if (err == hipSuccess)
+    err = hipMemcpy(sums, at<const double>(e->scratch, l.res), (size_t)l.cols * sizeof(double),
+                    hipMemcpyDeviceToHost);
+  if (err != hipSuccess) return hip_fail("pbh_trace_cov", err);
+  pbh::cov_finish(K, sums, sums + d, n * count, (int32_t)d, mean, cov, corr);
+  return PBH_OK;
+}
+
 int pbh_trace_quantile_pooled(pbh_engine *e, int64_t first, int64_t count, int32_t nq,
                               const double *q, double *out, double *order_stats) {
   if (const int rc = trace_enter(e, {{q, "q"}, {out, "out"}}, true, first, count, 1,

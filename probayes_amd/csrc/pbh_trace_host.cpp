@@ -309,4 +309,52 @@ TailLayout tail_layout(int64_t tiles, int64_t capacity) {
   return l;
 }
 
+bool cov_layout(int64_t n, int64_t count, int32_t d, CovLayout *out) {
+  int64_t draws;
+  if (n < 1 || count < 1 || d < 1 || d > PBH_MAX_DIM) return false;
+  if (__builtin_mul_overflow(n, count, &draws)) return false;
+  CovLayout l;
+  l.chain_blocks = n / kCovLanes + (n % kCovLanes != 0);
+  if (l.chain_blocks > 0x7fffffff) return false;
+  // above one tile: the two diagonal tiles, and per kCovHalf dims of the second
+  // a rectangle for either half of the first
+  l.pairs = d <= kCovTile
+                ? 1
+                : 2 + kCovTile / kCovHalf * ((d - kCovTile + kCovHalf - 1) / kCovHalf);
+  const int64_t groups = l.chain_blocks * l.pairs;
+  const int64_t want = std::min(count, (kPointwiseGroups + groups - 1) / groups);
+  l.slice_len = (count + want - 1) / want;
+  l.slices = (count + l.slice_len - 1) / l.slice_len;
+  l.rows = l.chain_blocks * l.slices;
+  l.cols = (int64_t)d + (int64_t)d * (d + 1) / 2;
+  int64_t at = 0;
+  const auto take = [&at](int64_t bytes) {
+    const int64_t here = at;
+    at += (bytes + 255) / 256 * 256;
+    return here;
+  };
+  l.K = take((int64_t)d * 8);
+  l.part = take(l.rows * l.cols * 8);
+  l.res = take(l.cols * 8);
+  l.bytes = at;
+  *out = l;
+  return true;
+}
+
+void cov_finish(const double *K, const double *S, const double *P, int64_t M, int32_t d,
+                double *mean, double *cov, double *corr) {
+  const double m = (double)M;
+  double c[PBH_MAX_DIM * PBH_MAX_DIM];
+  if (mean)
+    for (int32_t a = 0; a < d; ++a) mean[a] = K[a] + S[a] / m;
+  for (int32_t a = 0; a < d; ++a)
+    for (int32_t b = a; b < d; ++b)
+      c[a * d + b] = c[b * d + a] = (P[cov_tri(a, b, d)] - S[a] * S[b] / m) / (m - 1.);
+  if (cov) memcpy(cov, c, (size_t)d * d * sizeof(double));
+  if (corr)
+    for (int32_t a = 0; a < d; ++a)
+      for (int32_t b = a; b < d; ++b)
+        corr[a * d + b] = corr[b * d + a] = c[a * d + b] / std::sqrt(c[a * d + a] * c[b * d + b]);
+}
+
 }  // namespace pbh

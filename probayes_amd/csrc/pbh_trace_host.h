@@ -194,4 +194,41 @@ TailLayout tail_layout(int64_t tiles, int64_t capacity);
 // max(2 k, 65 536)
 int64_t tail_default_capacity(int64_t k);
 
+// The pooled covariance (pbh_cov.hip): the sums S_a of v_a and P_ab (a <= b) of
+// v_a v_b over every chain and record of a window, v = x - K, K the mean over
+// chains of the window's first record.  The dims go in tiles of at most
+// kCovTile: up to kCovTile dims one tile holds S and the whole triangle; above,
+// `pairs` tile jobs -- the two diagonal tiles of kCovTile dims (S and the
+// tile's triangle) and the rectangles of kCovHalf x kCovHalf dims between
+// them -- each read their dims of the window once.  A workgroup owns one block of kCovLanes
+// chains, one tile job and one slice of slice_len consecutive records (the
+// last slice may be shorter); the record slices fill the device when chains
+// are few, as pointwise_layout's do: as many as bring the grid to
+// kPointwiseGroups workgroups, at most one per record.  The workgroups of a
+// (chain block, slice) fill one partial row, row = chain block * slices +
+// slice, of cols = d + d (d + 1) / 2 doubles: S [d], then P's upper triangle
+// row by row (cov_tri).  The scratch, each offset a multiple of 256, the
+// regions disjoint and in this order: K [d], part [rows][cols], res [cols].
+constexpr int kCovLanes = 256, kCovTile = 16, kCovHalf = 8;
+struct CovLayout {
+  int64_t pairs, chain_blocks, slices, slice_len, rows, cols;
+  int64_t K, part, res, bytes;
+};
+// where P_ab, a <= b < d, lies in the packed triangle
+constexpr int64_t cov_tri(int64_t a, int64_t b, int64_t d) {
+  return a * d - a * (a - 1) / 2 + (b - a);
+}
+// False when an argument is out of range (n, count < 1, d outside 1 ..
+// PBH_MAX_DIM), n count leaves int64, or the chain blocks exceed a grid's 2^31
+// - 1; `out` is then untouched.
+bool cov_layout(int64_t n, int64_t count, int32_t d, CovLayout *out);
+// The last step, from the merged sums over M draws: mean [d] = K + S / M, cov
+// [d][d] = (P_ab - S_a S_b / M) / (M - 1) for a <= b and mirrored, corr [d][d]
+// = cov_ab / sqrt(cov_aa cov_bb), the diagonal included (1, or NaN for a dim
+// that never moves) -- diag.pooled_cov_finish in exactly its operation order,
+// so the two give the same bits.  P: the packed triangle.  Any of the three
+// results may be null.
+void cov_finish(const double *K, const double *S, const double *P, int64_t M, int32_t d,
+                double *mean, double *cov, double *corr);
+
 }  // namespace pbh

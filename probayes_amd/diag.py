@@ -38,6 +38,11 @@ Stephens 2009): per observation the smallest terms and the log-sum-exp of the
 rest (pbh_trace_pointwise_tail, Engine.trace_pointwise_tail), and elpd_loo and
 the Pareto shape from those.  compare_elpd is the difference of two models'
 pointwise rows, WAIC's or LOO's, with its standard error.
+
+pooled_cov and pooled_cov_finish are the definition of the posterior covariance
+and correlation pooled over chains and records (pbh_trace_cov, Engine.
+trace_cov), and proposal_cov turns such a matrix into the covariance of a
+random-walk proposal (Sampler.trace_tran, for RF.set_tran).
 """
 import math
 
@@ -642,3 +647,96 @@ def compare_elpd(a_i, b_i):
     raise ValueError('compare_elpd: two rows [n], got {} and {}'.format(a_i.shape, b_i.shape))
   diff = a_i - b_i
   return float(diff.sum()), float(np.sqrt(diff.size * np.var(diff)))
+
+
+def pooled_cov_finish(K, S, P, M):
+  """{'mean': [d], 'cov': [d, d], 'corr': [d, d]} from the sums over M draws of
+  v = x - K: S [d] = sum v_a and P, the upper triangle of sum v_a v_b packed row
+  by row (np.triu_indices order; a full [d, d] is read above its diagonal).
+  mean = K + S / M; cov_ab = (P_ab - S_a S_b / M) / (M - 1) for a <= b and
+  mirrored; corr_ab = cov_ab / sqrt(cov_aa cov_bb), the diagonal included (1,
+  or NaN for a dim that never moves).  Sums of several ranks taken about one K
+  add before this step."""
+  K, S = np.asarray(K, float).ravel(), np.asarray(S, float).ravel()
+  d = K.size
+  P = np.asarray(P, float)
+  ia, ib = np.triu_indices(d)
+  if P.shape == (d, d) and d > 1:
+    P = P[ia, ib]
+  P = P.ravel()
+  if S.size != d or P.size != d * (d + 1) // 2 or d < 1:
+    raise ValueError('pooled_cov_finish: K [d], S [d] and P [d (d + 1) / 2], got {}, {} and '
+                     '{}'.format(K.shape, S.shape, P.shape))
+  if int(M) < 2:
+    raise ValueError('pooled_cov_finish: M = {}: a covariance needs at least 2 '
+                     'draws'.format(M))
+  m = float(int(M))
+  cov, corr = np.empty((d, d)), np.empty((d, d))
+  with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+    mean = K + S / m
+    tri = (P - S[ia] * S[ib] / m) / (m - 1.)
+    cov[ia, ib] = tri
+    cov[ib, ia] = tri
+    var = np.diagonal(cov)
+    r = tri / np.sqrt(var[ia] * var[ib])
+    corr[ia, ib] = r
+    corr[ib, ia] = r
+  return {'mean': mean, 'cov': cov, 'corr': corr}
+
+
+def pooled_cov(x, first=0, count=None):
+  """{'mean': [d], 'cov': [d, d], 'corr': [d, d]}: the mean, the covariance
+  (ddof 1) and the correlation of a host trace x [N, T, d] over records [first,
+  first + count), pooled over every chain and record, M = N count draws.  The
+  sums are taken of v = x - K, K the mean over chains of the window's first
+  record: it lies within the cloud of draws, so S S / M cancels against P only
+  mildly wherever the posterior lies (sums of raw products lose everything once
+  the mean is large against the spread), and it costs no pass.  The values are
+  the IEEE results of pooled_cov_finish's formulas with no special cases:
+  constant and equal chains give cov exactly 0 and corr NaN, and a NaN record
+  propagates.  count >= 1, M >= 2."""
+  x, first, count = _window('pooled_cov', x, first, count)
+  if count < 1:
+    raise ValueError('pooled_cov: count = {}: at least 1 record'.format(count))
+  m = x.shape[0] * count
+  if m < 2:
+    raise ValueError('pooled_cov: {} chain of {} record: a covariance needs at least 2 '
+                     'draws'.format(x.shape[0], count))
+  d = x.shape[2]
+  w = x[:, first:first + count, :]
+  with np.errstate(invalid='ignore', over='ignore'):
+    K = w[:, 0, :].mean(axis=0)
+    # [d, M], the draws contiguous: NumPy's pairwise sum runs along them
+    v = np.ascontiguousarray((w - K).reshape(m, d).T)
+    S = v.sum(axis=1)
+    P = np.concatenate([(v[a:] * v[a]).sum(axis=1) for a in range(d)])
+  return pooled_cov_finish(K, S, P, m)
+
+
+def proposal_cov(cov, scale=None, eps=0.):
+  """[d, d]: the covariance of a random-walk proposal from a posterior
+  covariance: s (cov + eps mean(diag cov) I), s = 2.38^2 / d when scale is
+  None (Haario et al. 2001; Roberts & Rosenthal 2001: the optimal scale of a
+  Gaussian random walk on a Gaussian target) -- what RF.set_tran takes.  eps
+  lifts a covariance estimated from few draws off singularity.  ValueError
+  when the result is not a finite symmetric positive definite matrix (np.
+  linalg.cholesky fails on it)."""
+  cov = np.asarray(cov, float)
+  if cov.ndim != 2 or cov.shape[0] != cov.shape[1] or cov.shape[0] < 1:
+    raise ValueError('proposal_cov: a square matrix [d, d], got shape {}'.format(cov.shape))
+  d = cov.shape[0]
+  s = 2.38 ** 2 / d if scale is None else float(scale)
+  with np.errstate(invalid='ignore', over='ignore'):
+    out = s * (cov + float(eps) * np.mean(np.diagonal(cov)) * np.eye(d))
+  if not np.all(np.isfinite(out)):
+    raise ValueError('proposal_cov: the matrix has an entry that is not finite (a NaN or '
+                     'infinite draw, or a scale that is not finite)')
+  if not np.array_equal(out, out.T):
+    raise ValueError('proposal_cov: the matrix is not symmetric')
+  try:
+    np.linalg.cholesky(out)
+  except np.linalg.LinAlgError:
+    raise ValueError('proposal_cov: the matrix is not positive definite (a variable that '
+                     'never moved, variables that move as one, or fewer draws than '
+                     'variables; eps > 0 lifts it)')
+  return out

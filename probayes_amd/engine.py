@@ -809,6 +809,21 @@ class Engine:
               _dp(tail), _dp(rest), _c.byref(passes))
     return {'tail': tail, 'rest_lse': rest, 'passes': int(passes.value)}
 
+  def trace_cov(self, first=0, count=None):
+    """The posterior covariance of trace records [first, first + count) pooled
+    over every chain and record, computed on the device (diag.pooled_cov is the
+    definition): {'mean': [d], 'cov': [d, d], 'corr': [d, d]}.  The sums are
+    taken about the mean over chains of the window's first record, so a
+    posterior far from 0 costs no digits.  cov is symmetric in its bits; corr
+    has a diagonal of exactly 1, or NaN for a dim that never moves.  One pass
+    over the window; count >= 1, N count >= 2."""
+    first, count = self._window(first, count)
+    d = self.dim
+    mean, cov, corr = np.empty(d), np.empty((d, d)), np.empty((d, d))
+    _lib.call('pbh_trace_cov', self._h, _c.c_int64(int(first)), _c.c_int64(int(count)),
+              _dp(mean), _dp(cov), _dp(corr))
+    return {'mean': mean, 'cov': cov, 'corr': corr}
+
   def rccl_allreduce_max(self, value):
     v = _c.c_double(float(value))
     _lib.call('pbh_rccl_allreduce_max', self._h, _c.byref(v))

@@ -1495,6 +1495,59 @@ class Sampler:
     lse = self._eng.trace_pointwise(program, first, count)['lse']
     return diag.psis_loo_from_tail(tail['tail'], tail['rest_lse'], S, lse)
 
+  def trace_cov(self, first=0, count=None):
+    """How the names move together: the posterior mean, covariance and
+    correlation pooled over every chain and every record [first, first +
+    count), computed by the engine from its device trace (Engine.trace_cov)
+    without copying the trace to the host: {'names': [...], 'mean': {name:
+    value}, 'cov': [d, d], 'corr': [d, d]}, rows and columns in the order of
+    'names'.  N count >= 2.  Covers the sampler's first block while the engine
+    still holds it, as trace_quantile does."""
+    first, count = self._device_window('trace_cov', first, count)
+    if self._eng.n * count < 2:
+      raise ValueError('trace_cov: {} chain of {} record: a covariance needs at '
+                       'least 2 draws'.format(self._eng.n, count))
+    res = self._eng.trace_cov(first, count)
+    return {'names': list(self.names),
+            'mean': {k: float(res['mean'][i]) for i, k in enumerate(self.names)},
+            'cov': res['cov'], 'corr': res['corr']}
+
+  def _tran_refusal(self):
+    """Why the lowered proposal is not an additive Gaussian in the trace's
+    coordinates, so that a covariance of the trace is no proposal for it; None
+    when it is one."""
+    spec = self.spec
+    if spec.get('kind') == 'linreg' or spec['proposal']['kind'] == 'gibbs':
+      return 'a Gibbs sampler draws from conditionals and takes no proposal matrix'
+    names, prop = spec['names'], spec['proposal']
+    ufun = [k for k, u in zip(names, spec['ufun']) if u]
+    if ufun:
+      return 'variable {} steps through a ufun (a change of variable), not in the ' \
+          'trace\'s coordinates'.format(ufun[0])
+    vint = [k for k, v in zip(names, prop.get('vint', ())) if v]
+    if vint:
+      return 'variable {} is an int: its step is truncated'.format(vint[0])
+    if prop.get('bound') is not None:
+      return 'the delta is bounded (bound=True): steps are clamped or bounce at the limits'
+    return None
+
+  def trace_tran(self, first=0, count=None, scale=None, eps=0.):
+    """A random-walk proposal covariance from the posterior so far: diag.
+    proposal_cov(trace_cov(first, count)['cov'], scale, eps) -- (2.38^2 / d) times
+    the pooled covariance by default (Haario et al. 2001; Roberts & Rosenthal
+    2001) -- [d, d] in the order of the names, ready for RF.set_tran of the next
+    run's model, whose deltas are N(0, 1) per variable.  ValueError, naming the
+    cause, for a sampler whose proposal is not an additive Gaussian step in the
+    trace's coordinates (a ufun or int variable, bound=True, Gibbs), and when
+    the matrix is not positive definite (chains that have not moved: a longer
+    first run, or eps > 0)."""
+    from probayes_amd import diag
+    if self.spec is not None:
+      why = self._tran_refusal()
+      if why:
+        raise ValueError('trace_tran: ' + why)
+    return diag.proposal_cov(self.trace_cov(first, count)['cov'], scale, eps)
+
   def trace_quantile_pooled(self, q, first=0, count=None):
     """The posterior quantiles q of every name, pooled over every chain and
     every record [first, first + count), computed by the engine from its
