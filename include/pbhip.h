@@ -696,6 +696,46 @@ int pbh_trace_pointwise_tail(pbh_engine *eng, int64_t first, int64_t count,
 int pbh_trace_cov(pbh_engine *eng, int64_t first, int64_t count, double *mean,
                   double *cov, double *corr);
 
+/* Posterior histograms over trace records [first, first + count) on the
+ * device, pooled over every chain and record (added within revision 2 as
+ * pbh_trace_cov was: PBH_ABI_REVISION did not change for them, look the
+ * symbols up).  probayes_amd/diag.py hist_bin, pooled_hist and pooled_hist2d
+ * are the definition.  A dim k with n_bins[k] = B > 0 has B + 1 strictly
+ * increasing finite edges e[0 .. B]; n_bins[k] = 0 skips the dim.  The bin of
+ * a value x:
+ *   bin i holds e[i] <= x < e[i + 1];
+ *   the last bin also holds x == e[B];
+ *   x < e[0] is below, x > e[B] is above, a NaN is NaN: none of them is in a
+ *   bin;
+ *   plain comparisons: -0.0 and +0.0 are one value, -inf is below, +inf above.
+ * That is the rule of np.histogram(a, edges), of np.histogram(a, B, range =
+ * (lo, hi)) with edges = np.linspace(lo, hi, B + 1), and of np.histogram2d
+ * with explicit edges; the counts equal NumPy's bit for bit: the only state is
+ * integer counts, which no order of adds changes.
+ * pbh_trace_hist: counts holds the listed dims' counts one after the other,
+ * n_bins[k] each; outside [d][3] (may be NULL) holds below, above and NaN per
+ * dim, 0 for a skipped dim, so that a dim's counts and its row of outside add
+ * up to N count.
+ * pbh_trace_hist2d: per pair (a, b) of dims, counts [B_a][B_b] holds the draws
+ * with x_a in bin i of dim a and x_b in bin j of dim b; a draw with either
+ * value outside its bins is dropped.  a == b is allowed.  The pairs' grids lie
+ * one after the other.
+ * PBH_ERR_ARG, the message naming the dim or the pair and the index: counts
+ * NULL (whatever else was given), every n_bins[k] 0, an n_bins[k] below 0 or
+ * above PBH_HIST_MAX_BINS, an edge that is not finite, edges that do not
+ * strictly increase; for pairs n_pairs outside 1 .. 65 535, a dim outside [0,
+ * d), a dim without edges, B_a B_b above PBH_HIST2D_MAX_CELLS.  count >= 1.
+ * Two calls give the same counts.  Changes nothing in the engine: not the
+ * moments, the ESS, the trace, the chains or the generators.                */
+#define PBH_HIST_MAX_BINS 4096        /* per dim */
+#define PBH_HIST2D_MAX_CELLS 16384    /* B_a * B_b of a pair: 64 KiB of uint32 */
+int pbh_trace_hist(pbh_engine *eng, int64_t first, int64_t count,
+                   const int32_t *n_bins, const double *edges, int64_t *counts,
+                   int64_t *outside);
+int pbh_trace_hist2d(pbh_engine *eng, int64_t first, int64_t count,
+                     const int32_t *n_bins, const double *edges,
+                     int32_t n_pairs, const int32_t *pairs, int64_t *counts);
+
 /* ---- multi-GPU: one RCCL all-gather over xGMI --------- */
 int pbh_rccl_unique_id(uint8_t id[128]);
 int pbh_rccl_init(pbh_engine *eng, int32_t rank, int32_t world,

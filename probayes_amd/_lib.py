@@ -186,6 +186,12 @@ SIGNATURES = {
     # (likewise within revision 2)
     'pbh_trace_cov': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
                                      ctypes.c_int64, _dp, _dp, _dp]),
+    # (likewise within revision 2)
+    'pbh_trace_hist': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
+                                      ctypes.c_int64, _ip, _dp, _i64p, _i64p]),
+    'pbh_trace_hist2d': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_int64, _ip, _dp, ctypes.c_int32,
+                                        _ip, _i64p]),
     'pbh_trace_ess':(ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
                                      ctypes.c_int64, _dp]),
     'pbh_rccl_allreduce_max': (ctypes.c_int, [ctypes.c_void_p, _dp]),

@@ -353,6 +353,24 @@ hipError_t launch_tail_gather(const TailLaunch &t, int32_t done, hipStream_t s);
 struct CovLayout;
 hipError_t launch_cov(const double *tx, int64_t n, int32_t d, int64_t first, int64_t count,
                       unsigned char *scratch, const CovLayout &l, hipStream_t s);
+// The pooled histograms of trace records [first, first + count) (pbh_hist.hip):
+// integer counts alone, equal to NumPy's whatever the order of the adds.  l:
+// hist_layout's / hist2d_layout's dim groups, slices and offsets into scratch
+// (pbh_trace_host.h); plan [d]: every dim's lookup (hist_dim_plan).  The caller
+// has put the lookup tables at scratch + l.tables (hist_fill_table per listed
+// dim, in the layout's order) and, for the pairs, their records at scratch +
+// l.pairs; both launches clear the counters at scratch + l.counts on the stream
+// first.  launch_hist leaves per listed dim bins + 3 uint64 (the bins, then
+// below, above, NaN), launch_hist2d per pair B_a B_b uint64, row-major.
+struct HistLayout;
+struct Hist2dLayout;
+struct HistDimPlan;
+hipError_t launch_hist(const double *tx, int64_t n, int32_t d, int64_t first, int64_t count,
+                       unsigned char *scratch, const HistLayout &l, const HistDimPlan *plan,
+                       hipStream_t s);
+hipError_t launch_hist2d(const double *tx, int64_t n, int32_t d, int64_t first, int64_t count,
+                         unsigned char *scratch, const Hist2dLayout &l, const HistDimPlan *plan,
+                         hipStream_t s);
 // fft: 2 = the 2 048-point FFT form for count <= 1 536 records with the
 // 4 096-point form for the pairs it cannot decide (list: (d n + 1) / 2 + 1
 // int32 of device scratch), 1 = the 4 096-point form for count <= 2 048

@@ -334,6 +334,142 @@ int pbh_trace_cov(pbh_engine *e, int64_t first, int64_t count, double *mean, dou
   return PBH_OK;
 }
 
+int pbh_trace_hist(pbh_engine *e, int64_t first, int64_t count, const int32_t *n_bins,
+                   const double *edges, int64_t *counts, int64_t *outside) {
+  if (!counts)
+    return fail(PBH_ERR_ARG, "pbh_trace_hist: no output asked for (counts is NULL)");
+  const auto own = [&] {
+    const std::string bad = pbh::hist_check_edges((int32_t)e->d, n_bins, edges);
+    return bad.empty() ? PBH_OK : fail(PBH_ERR_ARG, "pbh_trace_hist: %s", bad.c_str());
+  };
+  if (const int rc = trace_enter(e, {{n_bins, "n_bins"}, {edges, "edges"}}, true, first, count, 1,
+                                 own))
+    return rc;
+  const int64_t n = e->n;
+  const int32_t d = (int32_t)e->d;
+  pbh::HistLayout l;
+  if (!pbh::hist_layout(n, count, d, n_bins, &l))
+    return fail(PBH_ERR_ARG, "pbh_trace_hist: no scratch layout for %lld chains of %lld records",
+                (long long)n, (long long)count);
+  HIP_TRY(hipSetDevice(e->device));
+  if (const int rc = scratch(e, (size_t)l.bytes)) return rc;
+  // the tables go up and the counts come back through the pinned stage (the
+  // tables, then the counts): queued copies, one wait
+  if (const int rc = stage(e, (size_t)(l.n_tab + l.n_ctr))) return rc;
+  double *tables = e->stage;
+  const uint64_t *host = reinterpret_cast<const uint64_t *>(e->stage + l.n_tab);
+  // every dim's lookup, and the listed dims' tables in the layout's order
+  pbh::HistDimPlan plan[PBH_MAX_DIM];
+  {
+    const double *ed = edges;
+    double *t = tables;
+    for (int32_t k = 0; k < d; ++k) {
+      plan[k] = pbh::hist_dim_plan(ed, n_bins[k]);
+      if (n_bins[k] == 0) continue;
+      pbh::hist_fill_table(ed, plan[k], t);
+      t += pbh::hist_table_len(n_bins[k]);
+      ed += n_bins[k] + 1;
+    }
+  }
+  hipError_t err = hipMemcpyAsync(at<double>(e->scratch, l.tables), tables,
+                                  (size_t)l.n_tab * sizeof(double), hipMemcpyHostToDevice,
+                                  e->stream);
+  if (err == hipSuccess)
+    err = pbh::launch_hist(e->tx, n, d, first, count, e->scratch, l, plan, e->stream);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(e->stage + l.n_tab, at<const uint64_t>(e->scratch, l.counts),
+                         (size_t)l.n_ctr * 8, hipMemcpyDeviceToHost, e->stream);
+  // (the stage is the source and the target of queued copies: waited for on
+  // every path)
+  const hipError_t drained = pbh::stream_wait(e);
+  if (err == hipSuccess) err = drained;
+  if (err != hipSuccess) return hip_fail("pbh_trace_hist", err);
+  // per listed dim: the bins, then below, above, NaN
+  if (outside) std::fill(outside, outside + 3 * (size_t)d, (int64_t)0);
+  const uint64_t *h = host;
+  for (int32_t k = 0; k < d; ++k) {
+    const int32_t B = n_bins[k];
+    if (B == 0) continue;
+    for (int32_t i = 0; i < B; ++i) *counts++ = (int64_t)h[i];
+    if (outside)
+      for (int i = 0; i < 3; ++i) outside[3 * k + i] = (int64_t)h[B + i];
+    h += B + 3;
+  }
+  return PBH_OK;
+}
+
+int pbh_trace_hist2d(pbh_engine *e, int64_t first, int64_t count, const int32_t *n_bins,
+                     const double *edges, int32_t n_pairs, const int32_t *pairs,
+                     int64_t *counts) {
+  if (!counts)
+    return fail(PBH_ERR_ARG, "pbh_trace_hist2d: no output asked for (counts is NULL)");
+  const auto own = [&] {
+    std::string bad = pbh::hist_check_edges((int32_t)e->d, n_bins, edges);
+    if (bad.empty()) bad = pbh::hist2d_check_pairs((int32_t)e->d, n_bins, n_pairs, pairs);
+    return bad.empty() ? PBH_OK : fail(PBH_ERR_ARG, "pbh_trace_hist2d: %s", bad.c_str());
+  };
+  if (const int rc = trace_enter(e, {{n_bins, "n_bins"}, {edges, "edges"}, {pairs, "pairs"}}, true,
+                                 first, count, 1, own))
+    return rc;
+  const int64_t n = e->n;
+  const int32_t d = (int32_t)e->d;
+  pbh::Hist2dLayout l;
+  if (!pbh::hist2d_layout(n, count, d, n_bins, n_pairs, pairs, &l))
+    return fail(PBH_ERR_ARG, "pbh_trace_hist2d: no scratch layout for %lld chains of %lld "
+                "records", (long long)n, (long long)count);
+  HIP_TRY(hipSetDevice(e->device));
+  if (const int rc = scratch(e, (size_t)l.bytes)) return rc;
+  // the tables and the pairs' records go up through the pinned stage, and the
+  // counts come back through it while they are few (kStagedCounts: 16 MB): queued
+  // copies, one wait.  More counts are copied to the caller after the wait.
+  constexpr int64_t kStagedCounts = (int64_t)1 << 21;
+  const bool staged = l.n_ctr <= kStagedCounts;
+  const int64_t up = l.n_tab + 4 * (int64_t)n_pairs;
+  if (const int rc = stage(e, (size_t)(up + (staged ? l.n_ctr : 0)))) return rc;
+  double *tables = e->stage;
+  int64_t *recs = reinterpret_cast<int64_t *>(e->stage + l.n_tab);
+  pbh::HistDimPlan plan[PBH_MAX_DIM];
+  {
+    const double *ed = edges;
+    for (int32_t k = 0; k < d; ++k) {
+      plan[k] = pbh::hist_dim_plan(ed, n_bins[k]);
+      if (n_bins[k] == 0) continue;
+      pbh::hist_fill_table(ed, plan[k], tables + l.tab_off[k]);
+      ed += n_bins[k] + 1;
+    }
+  }
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    recs[(size_t)p * 4] = pairs[2 * p];
+    recs[(size_t)p * 4 + 1] = pairs[2 * p + 1];
+    recs[(size_t)p * 4 + 2] = l.out[(size_t)p];
+    recs[(size_t)p * 4 + 3] = 0;
+  }
+  hipError_t err = hipMemcpyAsync(at<double>(e->scratch, l.tables), tables,
+                                  (size_t)l.n_tab * sizeof(double), hipMemcpyHostToDevice,
+                                  e->stream);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(at<int64_t>(e->scratch, l.pairs), recs, (size_t)n_pairs * 4 * 8,
+                         hipMemcpyHostToDevice, e->stream);
+  if (err == hipSuccess)
+    err = pbh::launch_hist2d(e->tx, n, d, first, count, e->scratch, l, plan, e->stream);
+  if (err == hipSuccess && staged)
+    err = hipMemcpyAsync(e->stage + up, at<const uint64_t>(e->scratch, l.counts),
+                         (size_t)l.n_ctr * 8, hipMemcpyDeviceToHost, e->stream);
+  // (the stage is the source and the target of queued copies: waited for on
+  // every path)
+  const hipError_t drained = pbh::stream_wait(e);
+  if (err == hipSuccess) err = drained;
+  // the pairs' cells lie one after the other, as the caller's do; a count is
+  // below 2^63, so its uint64 is the caller's int64
+  if (err == hipSuccess && staged)
+    std::memcpy(counts, e->stage + up, (size_t)l.n_ctr * 8);
+  else if (err == hipSuccess)
+    err = hipMemcpy(counts, at<const uint64_t>(e->scratch, l.counts), (size_t)l.n_ctr * 8,
+                    hipMemcpyDeviceToHost);
+  if (err != hipSuccess) return hip_fail("pbh_trace_hist2d", err);
+  return PBH_OK;
+}
+
 int pbh_trace_quantile_pooled(pbh_engine *e, int64_t first, int64_t count, int32_t nq,
                               const double *q, double *out, double *order_stats) {
   if (const int rc = trace_enter(e, {{q, "q"}, {out, "out"}}, true, first, count, 1,

@@ -357,4 +357,220 @@ void cov_finish(const double *K, const double *S, const double *P, int64_t M, in
         corr[a * d + b] = corr[b * d + a] = c[a * d + b] / std::sqrt(c[a * d + a] * c[b * d + b]);
 }
 
+static_assert(kHistMaxDims == PBH_MAX_DIM, "a dim group list per engine dim");
+static_assert(((int64_t)1 << kHistMaxDepth) == PBH_HIST_MAX_BINS, "the deepest search");
+static_assert(kHistLanes * kHistMaxSlice < ((int64_t)1 << 32), "a workgroup's uint32 counter");
+
+std::string hist_check_edges(int32_t d, const int32_t *n_bins, const double *edges) {
+  char buf[160];
+  buf[0] = 0;
+  bool any = false;
+  const double *e = edges;
+  for (int32_t k = 0; k < d; ++k) {
+    const int32_t B = n_bins[k];
+    if (B < 0 || B > PBH_HIST_MAX_BINS) {
+      snprintf(buf, sizeof buf, "dim %d: n_bins = %d outside 0..%d", (int)k, (int)B,
+               PBH_HIST_MAX_BINS);
+      return buf;
+    }
+    if (B == 0) continue;
+    any = true;
+    for (int32_t i = 0; i <= B; ++i) {
+      if (!std::isfinite(e[i])) {
+        snprintf(buf, sizeof buf, "dim %d: edge %d = %g is not finite", (int)k, (int)i, e[i]);
+        return buf;
+      }
+      if (i > 0 && !(e[i - 1] < e[i])) {
+        snprintf(buf, sizeof buf, "dim %d: edge %d = %.17g does not lie above edge %d = %.17g "
+                 "(the edges strictly increase)", (int)k, (int)i, e[i], (int)i - 1, e[i - 1]);
+        return buf;
+      }
+    }
+    e += B + 1;
+  }
+  if (!any) snprintf(buf, sizeof buf, "every n_bins[k] of the %d dims is 0: no dim to count", (int)d);
+  return buf;
+}
+
+bool hist_guess_ok(const double *e, int32_t bins) {
+  if (bins < 1) return false;
+  const double e0 = e[0], s = (double)bins / (e[bins] - e0);
+  if (!std::isfinite(s) || !(s > 0.)) return false;
+  for (int32_t i = 0; i < bins; ++i) {
+    const double last = std::nextafter(e[i + 1], -std::numeric_limits<double>::infinity());
+    const int32_t lo = hist_guess(bins, e0, s, e[i]), hi = hist_guess(bins, e0, s, last);
+    if (lo < i - 1 || lo > i + 1 || hi < i - 1 || hi > i + 1) return false;
+  }
+  return true;
+}
+
+HistDimPlan hist_dim_plan(const double *e, int32_t bins) {
+  HistDimPlan p{bins, 0, 0., 0., 0.};
+  if (bins < 1) return p;
+  p.e0 = e[0];
+  p.eB = e[bins];
+  if (hist_guess_ok(e, bins)) {
+    p.mode = kHistGuess;
+    p.s = (double)bins / (p.eB - p.e0);
+  } else {
+    p.mode = hist_depth(bins);
+  }
+  return p;
+}
+
+void hist_fill_table(const double *e, const HistDimPlan &p, double *t) {
+  const int64_t len = hist_table_len(p.bins);
+  const double inf = std::numeric_limits<double>::infinity();
+  // the guess reads e[0 .. bins]; the search e[0 .. bins - 1] and the padding
+  const int64_t held = p.mode == kHistGuess ? (int64_t)p.bins + 1 : (int64_t)p.bins;
+  for (int64_t i = 0; i < len; ++i) t[i] = i < held ? e[i] : inf;
+}
+
+namespace {
+
+// the chain blocks and the record slices of a histogram's grid of `groups`
+// jobs per (chain block, slice)
+bool hist_slices(int64_t n, int64_t count, int64_t groups, int64_t *chain_blocks, int64_t *slices,
+                 int64_t *slice_len) {
+  int64_t draws;
+  if (n < 1 || count < 1 || groups < 1) return false;
+  if (__builtin_mul_overflow(n, count, &draws)) return false;
+  const int64_t blocks = n / kHistLanes + (n % kHistLanes != 0);
+  if (blocks > 0x7fffffff) return false;
+  int64_t jobs;
+  if (__builtin_mul_overflow(blocks, groups, &jobs)) return false;
+  const int64_t want = std::min(count, (kPointwiseGroups + jobs - 1) / jobs);
+  const int64_t len = std::min((count + want - 1) / want, kHistMaxSlice);
+  const int64_t s = (count + len - 1) / len;
+  if (s > 65535) return false;
+  *chain_blocks = blocks;
+  *slices = s;
+  *slice_len = len;
+  return true;
+}
+
+int64_t hist_dim_lds(int32_t bins) {
+  return (8 * hist_table_len(bins) + 4 * ((int64_t)bins + 3) + 7) / 8 * 8;
+}
+
+}  // namespace
+
+bool hist_layout(int64_t n, int64_t count, int32_t d, const int32_t *n_bins, HistLayout *out) {
+  if (d < 1 || d > kHistMaxDims) return false;
+  HistLayout l;
+  memset(&l, 0, sizeof l);
+  int64_t room = 0;   // what the open group may still take; 0: none is open
+  for (int32_t k = 0; k < d; ++k) {
+    const int32_t B = n_bins[k];
+    if (B < 0 || B > PBH_HIST_MAX_BINS) return false;
+    if (B == 0) continue;
+    const int64_t need = hist_dim_lds(B);
+    const bool alone = need > kHistLdsBudget / 2;
+    if (alone || need > room) {
+      // a new group
+      l.group_first[l.groups] = l.dims;
+      l.tab_off[l.groups] = (int32_t)l.n_tab;
+      l.ctr_off[l.groups] = (int32_t)l.n_ctr;
+      ++l.groups;
+      room = alone ? need : kHistLdsBudget;
+    }
+    const int32_t g = l.groups - 1, j = l.dims++;
+    l.dim[j] = k;
+    l.tab[j] = l.tab_len[g];
+    l.ctr[j] = l.ctr_len[g];
+    l.tab_len[g] += (int32_t)hist_table_len(B);
+    l.ctr_len[g] += B + 3;
+    l.n_tab += hist_table_len(B);
+    l.n_ctr += B + 3;
+    room -= need;
+  }
+  if (l.dims == 0) return false;
+  l.group_first[l.groups] = l.dims;
+  for (int32_t g = 0; g < l.groups; ++g)
+    l.lds_bytes = std::max(l.lds_bytes, ((int64_t)8 * l.tab_len[g] + 4 * l.ctr_len[g] + 7) / 8 * 8);
+  if (!hist_slices(n, count, l.groups, &l.chain_blocks, &l.slices, &l.slice_len)) return false;
+  int64_t at = 0;
+  const auto take = [&at](int64_t bytes) {
+    const int64_t here = at;
+    at += (bytes + 255) / 256 * 256;
+    return here;
+  };
+  l.tables = take(l.n_tab * 8);
+  l.counts = take(l.n_ctr * 8);
+  l.bytes = at;
+  *out = l;
+  return true;
+}
+
+std::string hist2d_check_pairs(int32_t d, const int32_t *n_bins, int32_t n_pairs,
+                               const int32_t *pairs) {
+  char buf[160];
+  buf[0] = 0;
+  if (n_pairs < 1 || n_pairs > 65535) {
+    snprintf(buf, sizeof buf, "n_pairs = %d outside 1..65535", (int)n_pairs);
+    return buf;
+  }
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    for (int side = 0; side < 2; ++side) {
+      const int32_t k = pairs[2 * p + side];
+      if (k < 0 || k >= d) {
+        snprintf(buf, sizeof buf, "pair %d: dim %d outside [0, %d)", (int)p, (int)k, (int)d);
+        return buf;
+      }
+      if (n_bins[k] < 1) {
+        snprintf(buf, sizeof buf, "pair %d: dim %d has no edges (n_bins = %d)", (int)p, (int)k,
+                 (int)n_bins[k]);
+        return buf;
+      }
+    }
+    const int64_t cells = (int64_t)n_bins[pairs[2 * p]] * n_bins[pairs[2 * p + 1]];
+    if (cells > PBH_HIST2D_MAX_CELLS) {
+      snprintf(buf, sizeof buf, "pair %d: dims %d and %d make %d x %d = %lld cells, above %d",
+               (int)p, (int)pairs[2 * p], (int)pairs[2 * p + 1], (int)n_bins[pairs[2 * p]],
+               (int)n_bins[pairs[2 * p + 1]], (long long)cells, PBH_HIST2D_MAX_CELLS);
+      return buf;
+    }
+  }
+  return buf;
+}
+
+bool hist2d_layout(int64_t n, int64_t count, int32_t d, const int32_t *n_bins, int32_t n_pairs,
+                   const int32_t *pairs, Hist2dLayout *out) {
+  if (d < 1 || d > kHistMaxDims) return false;
+  for (int32_t k = 0; k < d; ++k)
+    if (n_bins[k] < 0 || n_bins[k] > PBH_HIST_MAX_BINS) return false;
+  if (!hist2d_check_pairs(d, n_bins, n_pairs, pairs).empty()) return false;
+  Hist2dLayout l;
+  l.n_pairs = n_pairs;
+  l.n_tab = l.n_ctr = l.lds_bytes = 0;
+  for (int32_t k = 0; k < kHistMaxDims; ++k) {
+    l.tab_off[k] = -1;
+    if (k < d && n_bins[k] > 0) {
+      l.tab_off[k] = (int32_t)l.n_tab;
+      l.n_tab += hist_table_len(n_bins[k]);
+    }
+  }
+  l.out.resize((size_t)n_pairs);
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    const int32_t Ba = n_bins[pairs[2 * p]], Bb = n_bins[pairs[2 * p + 1]];
+    l.out[(size_t)p] = l.n_ctr;
+    l.n_ctr += (int64_t)Ba * Bb;
+    l.lds_bytes = std::max(l.lds_bytes,
+                           8 * (hist_table_len(Ba) + hist_table_len(Bb)) + ((int64_t)4 * Ba * Bb + 7) / 8 * 8);
+  }
+  if (!hist_slices(n, count, n_pairs, &l.chain_blocks, &l.slices, &l.slice_len)) return false;
+  int64_t at = 0;
+  const auto take = [&at](int64_t bytes) {
+    const int64_t here = at;
+    at += (bytes + 255) / 256 * 256;
+    return here;
+  };
+  l.tables = take(l.n_tab * 8);
+  l.pairs = take((int64_t)n_pairs * 4 * 8);
+  l.counts = take(l.n_ctr * 8);
+  l.bytes = at;
+  *out = std::move(l);
+  return true;
+}
+
 }  // namespace pbh

@@ -4,7 +4,9 @@
 // geometry and scratch layout of the pooled sort (pbh_rank.hip), and the layout
 // and the estimator of the ESS across chains (pbh_ess_rank.hip), the layout and
 // the merges of the pointwise reduction (pbh_pointwise.hip), and the pick and
-// the finish of its tail select (pbh_pointwise_tail.hip).  No HIP: a host
+// the finish of its tail select (pbh_pointwise_tail.hip), the layout and the
+// last step of the pooled covariance (pbh_cov.hip), and the checks, the choice
+// of lookup and the layouts of the pooled histograms (pbh_hist.hip).  No HIP: a host
 // compiler alone builds it (tests/trace_host_main.cpp, the one program the CPU
 // tests drive it through).  Built with -ffp-contract=off: the interpolation and
 // the estimator must round as NumPy's do.
@@ -14,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "pbh_hist_bin.h"
 #include "pbh_pointwise_merge.h"
 
 namespace pbh {
@@ -230,5 +233,92 @@ bool cov_layout(int64_t n, int64_t count, int32_t d, CovLayout *out);
 // results may be null.
 void cov_finish(const double *K, const double *S, const double *P, int64_t M, int32_t d,
                 double *mean, double *cov, double *corr);
+
+// The pooled histograms (pbh_hist.hip): per dim the counts of the draws of a
+// window in the bins of strictly increasing finite edges, and per pair of dims
+// the counts in the grid of the two dims' bins; pbh_hist_bin.h has the lookup.
+// n_bins [d]: B_k, 0 for a dim that is skipped; edges: the dims' B_k + 1 edges
+// one after the other.
+constexpr int kHistLanes = 256, kHistMaxDims = 32;   // (PBH_MAX_DIM)
+// what one workgroup's LDS holds of a dim group (two workgroups per CU of 160 KiB)
+constexpr int64_t kHistLdsBudget = 64 * 1024;
+// the records of a slice: a workgroup's uint32 counter takes at most kHistLanes
+// x kHistMaxSlice < 2^32 elements
+constexpr int64_t kHistMaxSlice = ((int64_t)1 << 24) - 1;
+// What is wrong with the edges, naming the dim and the index, or empty: an
+// n_bins[k] outside 0 .. PBH_HIST_MAX_BINS, every n_bins[k] 0, an edge that is
+// not finite, edges that do not strictly increase.
+std::string hist_check_edges(int32_t d, const int32_t *n_bins, const double *edges);
+// Whether the guess path of pbh_hist_bin.h is right for every double with these
+// edges e [bins + 1] (checked: strictly increasing, finite): s = bins / (e[bins] -
+// e[0]) is finite and above 0, and hist_guess lies within one of i at e[i] and
+// at the double just below e[i + 1], for every bin i.
+bool hist_guess_ok(const double *e, int32_t bins);
+// A dim's lookup: mode kHistGuess or the search's depth; s is read by the guess
+// alone.  bins == 0: a skipped dim, all 0.
+struct HistDimPlan {
+  int32_t bins, mode;
+  double e0, eB, s;
+};
+HistDimPlan hist_dim_plan(const double *e, int32_t bins);
+// The dim's table t [hist_table_len(bins)] for its mode (pbh_hist_bin.h).
+void hist_fill_table(const double *e, const HistDimPlan &p, double *t);
+
+// hist_layout: the listed dims (n_bins[k] > 0) in ascending order go in dim
+// groups of consecutive listed dims.  A listed dim takes lds(k) = 8
+// hist_table_len(B_k) + 4 (B_k + 3) bytes, rounded up to 8: its table and its
+// uint32 counters (the bins, then below, above, NaN).  A dim with lds(k) above
+// half of kHistLdsBudget is a group of its own; the others fill a group while
+// the sum stays within the budget.  A workgroup owns one block of kHistLanes
+// chains, one dim group and one slice of slice_len <= kHistMaxSlice consecutive
+// records (the last may be shorter): as many slices as bring the grid to
+// kPointwiseGroups workgroups, at most one per record, as cov_layout forms
+// them.  A group's LDS: its dims' tables one after the other, then their
+// counters one after the other; tab[j] / ctr[j] are where listed dim j's lie
+// among the group's, tab_off[g] / ctr_off[g] where the group's lie among all
+// (the same order in the scratch), tab_len[g] / ctr_len[g] how many.  The
+// scratch, each offset a multiple of 256, the regions disjoint and in this
+// order: tables (n_tab doubles), counts (n_ctr uint64).
+struct HistLayout {
+  int32_t dims, groups;
+  int32_t dim[kHistMaxDims], tab[kHistMaxDims], ctr[kHistMaxDims];                // per listed dim
+  int32_t group_first[kHistMaxDims + 1];                                           // listed dims
+  int32_t tab_off[kHistMaxDims], tab_len[kHistMaxDims], ctr_off[kHistMaxDims],     // per group
+      ctr_len[kHistMaxDims];
+  int64_t lds_bytes;   // of the largest group
+  int64_t chain_blocks, slices, slice_len, n_tab, n_ctr;
+  int64_t tables, counts, bytes;
+};
+// False when an argument is out of range (n, count < 1, d outside 1 ..
+// kHistMaxDims, an n_bins[k] outside 0 .. PBH_HIST_MAX_BINS, no dim listed), n
+// count leaves int64, the chain blocks exceed 2^31 - 1 or the slices a grid's
+// 65 535; `out` is then untouched.
+bool hist_layout(int64_t n, int64_t count, int32_t d, const int32_t *n_bins, HistLayout *out);
+
+// hist2d_layout: a workgroup owns one block of kHistLanes chains, one pair and
+// one slice of records, formed as above with the pairs in the groups' place.
+// Its LDS: the table of dim a, the table of dim b, the B_a B_b uint32 cells.
+// tab_off[k]: where dim k's table lies among the tables of the dims that have
+// edges (all of them, in ascending order), -1 without edges; out[p]: where the
+// pair's cells lie among the counts.  The scratch, each offset a multiple of
+// 256, the regions disjoint and in this order: tables (n_tab doubles), pairs
+// (n_pairs records of 4 int64: a, b, out, 0), counts (n_ctr uint64).
+struct Hist2dLayout {
+  int32_t n_pairs;
+  int32_t tab_off[kHistMaxDims];
+  std::vector<int64_t> out;
+  int64_t lds_bytes;   // of the largest pair
+  int64_t chain_blocks, slices, slice_len, n_tab, n_ctr;
+  int64_t tables, pairs, counts, bytes;
+};
+// What is wrong with the pairs [n_pairs][2], naming the pair, or empty: n_pairs
+// outside 1 .. 65 535, a dim outside [0, d), a dim without edges, B_a B_b above
+// PBH_HIST2D_MAX_CELLS.  a == b is allowed.
+std::string hist2d_check_pairs(int32_t d, const int32_t *n_bins, int32_t n_pairs,
+                               const int32_t *pairs);
+// False when an argument is out of range (as hist_layout's, and the pairs as
+// hist2d_check_pairs has them); `out` is then untouched.
+bool hist2d_layout(int64_t n, int64_t count, int32_t d, const int32_t *n_bins, int32_t n_pairs,
+                   const int32_t *pairs, Hist2dLayout *out);
 
 }  // namespace pbh

@@ -43,6 +43,13 @@ pooled_cov and pooled_cov_finish are the definition of the posterior covariance
 and correlation pooled over chains and records (pbh_trace_cov, Engine.
 trace_cov), and proposal_cov turns such a matrix into the covariance of a
 random-walk proposal (Sampler.trace_tran, for RF.set_tran).
+
+hist_bin, pooled_hist and pooled_hist2d are the definition of the posterior
+histograms pooled over chains and records (pbh_trace_hist, pbh_trace_hist2d,
+Engine.trace_hist, Engine.trace_hist2d): np.histogram's and np.histogram2d's
+counts.  hist_edges forms the edges from (bins, range) as np.histogram does,
+hist_density and hist2d_density divide the counts as density=True does
+(Sampler.trace_hist, trace_hist2d, trace_corner).
 """
 import math
 
@@ -739,4 +746,196 @@ def proposal_cov(cov, scale=None, eps=0.):
     raise ValueError('proposal_cov: the matrix is not positive definite (a variable that '
                      'never moved, variables that move as one, or fewer draws than '
                      'variables; eps > 0 lifts it)')
+  return out
+
+
+def _edges(what, edges):
+  e = np.asarray(edges, float)
+  if e.ndim != 1 or e.size < 2:
+    raise ValueError('{}: edges [B + 1] with B >= 1, got shape {}'.format(what, e.shape))
+  if not np.all(np.isfinite(e)):
+    raise ValueError('{}: an edge is not finite'.format(what))
+  if not np.all(e[:-1] < e[1:]):
+    raise ValueError('{}: the edges do not strictly increase'.format(what))
+  return e
+
+
+def hist_bin(x, edges):
+  """The bin of every value of x among strictly increasing finite edges [B +
+  1], an int64 array of x's shape: bin i holds edges[i] <= x < edges[i + 1], the
+  last bin also x == edges[B]; -1 is below edges[0], -2 above edges[B], -3 a
+  NaN.  Plain comparisons: -0.0 and +0.0 are one value, -inf is below and +inf
+  above.  This is where np.histogram(x, edges), np.histogram(x, B, range=(lo,
+  hi)) with edges = np.linspace(lo, hi, B + 1), and np.histogram2d with
+  explicit edges count a value."""
+  e = _edges('hist_bin', edges)
+  x = np.asarray(x, float)
+  nb = e.size - 1
+  # the edges that are <= x, less one (a NaN sorts behind every edge)
+  out = np.searchsorted(e, x, side='right').astype(np.int64) - 1
+  out = np.where(x == e[nb], nb - 1, out)
+  out = np.where(x < e[0], -1, out)
+  out = np.where(x > e[nb], -2, out)
+  return np.where(np.isnan(x), -3, out).astype(np.int64)
+
+
+def _edge_list(what, edges, d):
+  if len(edges) != d:
+    raise ValueError('{}: {} edge arrays for {} dims (None skips a dim)'.format(
+        what, len(edges), d))
+  return [None if e is None else _edges(what, e) for e in edges]
+
+
+def pooled_hist(x, edges, first=0, count=None):
+  """{'counts': [int64 [B_k] or None per dim], 'outside': int64 [d, 3]}: the
+  histograms of a host trace x [N, T, d] over records [first, first + count)
+  pooled over every chain and record (pbh_trace_hist, Engine.trace_hist).
+  edges: a list of d arrays, None for a dim to skip.  counts[k][i] is the number
+  of draws with hist_bin(x_k, edges[k]) == i; outside[k] the numbers below,
+  above and NaN (0 for a skipped dim), so that counts[k].sum() + outside[k].sum()
+  == N count."""
+  x, first, count = _window('pooled_hist', x, first, count)
+  if count < 1:
+    raise ValueError('pooled_hist: count = {}: at least 1 record'.format(count))
+  d = x.shape[2]
+  edges = _edge_list('pooled_hist', edges, d)
+  if all(e is None for e in edges):
+    raise ValueError('pooled_hist: every dim is skipped')
+  w = x[:, first:first + count, :]
+  counts, outside = [], np.zeros((d, 3), np.int64)
+  for k, e in enumerate(edges):
+    if e is None:
+      counts.append(None)
+      continue
+    b = hist_bin(w[:, :, k].ravel(), e)
+    counts.append(np.bincount(b[b >= 0], minlength=e.size - 1).astype(np.int64))
+    outside[k] = [(b == -1).sum(), (b == -2).sum(), (b == -3).sum()]
+  return {'counts': counts, 'outside': outside}
+
+
+def pooled_hist2d(x, edges, pairs, first=0, count=None):
+  """A list of int64 [B_a, B_b], one per (a, b) in pairs: H[i, j] counts the
+  draws of a host trace x [N, T, d] over records [first, first + count), pooled
+  over every chain and record, with hist_bin(x_a, edges[a]) == i and
+  hist_bin(x_b, edges[b]) == j; a draw with either bin negative is dropped --
+  np.histogram2d(x_a, x_b, bins=[edges[a], edges[b]]) (pbh_trace_hist2d, Engine.
+  trace_hist2d).  a == b is allowed."""
+  x, first, count = _window('pooled_hist2d', x, first, count)
+  if count < 1:
+    raise ValueError('pooled_hist2d: count = {}: at least 1 record'.format(count))
+  d = x.shape[2]
+  edges = _edge_list('pooled_hist2d', edges, d)
+  if len(pairs) < 1:
+    raise ValueError('pooled_hist2d: no pair')
+  w = x[:, first:first + count, :]
+  out = []
+  for a, b in pairs:
+    a, b = int(a), int(b)
+    if not (0 <= a < d and 0 <= b < d) or edges[a] is None or edges[b] is None:
+      raise ValueError('pooled_hist2d: pair ({}, {}) names a dim outside [0, {}) or one '
+                       'without edges'.format(a, b, d))
+    na, nb = edges[a].size - 1, edges[b].size - 1
+    ia = hist_bin(w[:, :, a].ravel(), edges[a])
+    ib = hist_bin(w[:, :, b].ravel(), edges[b])
+    keep = (ia >= 0) & (ib >= 0)
+    cells = np.bincount(ia[keep] * nb + ib[keep], minlength=na * nb)
+    out.append(cells.astype(np.int64).reshape(na, nb))
+  return out
+
+
+def _hist_edges_one(what, bins, rng, minmax):
+  """np.histogram's bin edges of one variable: bins an int (then rng (lo, hi),
+  or minmax() -> (lo, hi) of the data) or an edge array (rng is not read)."""
+  if np.ndim(bins) == 0:
+    try:
+      nb = int(bins)
+      whole = nb == bins
+    except (TypeError, ValueError):
+      whole = False
+    if not whole:
+      raise TypeError('{}: bins = {!r} is neither a whole number nor an edge array'.format(
+          what, bins))
+    if nb < 1:
+      raise ValueError('{}: bins = {}: at least 1'.format(what, nb))
+    if rng is not None:
+      lo, hi = (float(v) for v in rng)
+      if lo > hi:
+        raise ValueError('{}: range ({}, {}): max must be larger than min'.format(what, lo, hi))
+      if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError('{}: range ({}, {}) is not finite'.format(what, lo, hi))
+    else:
+      lo, hi = (float(v) for v in minmax())
+      if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError('{}: the values\' range [{}, {}] is not finite: give range=(lo, '
+                         'hi)'.format(what, lo, hi))
+    if lo == hi:
+      lo, hi = lo - 0.5, hi + 0.5
+    e = np.linspace(lo, hi, nb + 1)
+    if not (np.all(np.isfinite(e)) and np.all(e[:-1] < e[1:])):
+      raise ValueError('{}: {} bins over ({}, {}) do not give strictly increasing finite '
+                       'edges'.format(what, nb, lo, hi))
+    return e
+  return _edges(what, bins)
+
+
+def hist_edges(bins=10, range=None, names=None, minmax=None):
+  """The bin edges np.histogram forms from (bins, range), without the data.
+  One variable (names=None): bins is an int or an edge array, range (lo, hi) or
+  None, and the result one float64 array.  With an int: the edges are
+  np.linspace(lo, hi, bins + 1); lo == hi becomes lo - 0.5, hi + 0.5; with
+  range=None, (lo, hi) = minmax(), the smallest and the largest value of the
+  data, asked for only then.  An edge array is returned as float64; range is
+  not read.  names=[...]: bins may also be {name: int or array} -- a name left
+  out is skipped -- and range {name: (lo, hi)}; minmax() then returns {name:
+  (lo, hi)} and is called at most once; the result is a list in the order of
+  names, None for a skipped name.  ValueError as np.histogram: bins < 1, lo >
+  hi, a range or a data range that is not finite; and for edges that are not
+  finite or do not strictly increase (np.histogram takes equal edges; the
+  device does not)."""
+  what = 'hist_edges'
+  if names is None:
+    if isinstance(bins, dict) or isinstance(range, dict):
+      raise ValueError('hist_edges: a dict of bins or ranges needs names')
+    return _hist_edges_one(what, bins, range, minmax)
+  names = list(names)
+  for given in (bins, range):
+    if isinstance(given, dict):
+      unknown = [k for k in given if k not in names]
+      if unknown:
+        raise ValueError('hist_edges: {!r} is not one of the names {}'.format(unknown[0], names))
+  found = {}
+
+  def data_range(name):
+    if not found:
+      found.update(minmax())
+    return found[name]
+
+  out = []
+  for name in names:
+    if isinstance(bins, dict) and name not in bins:
+      out.append(None)
+      continue
+    b = bins[name] if isinstance(bins, dict) else bins
+    r = range.get(name) if isinstance(range, dict) else range
+    out.append(_hist_edges_one('hist_edges ({})'.format(name), b, r,
+                               lambda name=name: data_range(name)))
+  return out
+
+
+def hist_density(h, edges):
+  """np.histogram's density=True from the counts: h / np.diff(edges) / h.sum(),
+  in NumPy's operation order."""
+  h = np.asarray(h)
+  return h / np.diff(np.asarray(edges, float)) / h.sum()
+
+
+def hist2d_density(h, xedges, yedges):
+  """np.histogram2d's H from the counts [B_x, B_y]: float64, and with density
+  divided by the bins' widths along x, then along y, then by the sum, in
+  NumPy's operation order."""
+  out = np.asarray(h).astype(float)
+  s = out.sum()
+  out = out / np.diff(np.asarray(xedges, float)).reshape(-1, 1)
+  out = out / np.diff(np.asarray(yedges, float)).reshape(1, -1)
+  out /= s
   return out

@@ -824,6 +824,75 @@ class Engine:
               _dp(mean), _dp(cov), _dp(corr))
     return {'mean': mean, 'cov': cov, 'corr': corr}
 
+  def _hist_args(self, what, edges):
+    """edges, a list of d arrays or None, as the C-ABI takes them: (n_bins
+    int32 [d], the dims' edges one after the other).  The library checks the
+    edges themselves."""
+    if len(edges) != self.dim:
+      raise ValueError('{}: {} edge arrays for {} dims (None skips a dim)'.format(
+          what, len(edges), self.dim))
+    arrays = [None if e is None else _f64(e).ravel() for e in edges]
+    for k, e in enumerate(arrays):
+      if e is not None and e.size < 2:
+        raise ValueError('{}: dim {} has {} edges, a bin needs 2'.format(what, k, e.size))
+    n_bins = _i32([0 if e is None else e.size - 1 for e in arrays])
+    flat = _f64(np.concatenate([e for e in arrays if e is not None] or [np.zeros(1)]))
+    return arrays, n_bins, flat
+
+  def trace_hist(self, edges, first=0, count=None):
+    """The histograms of trace records [first, first + count) pooled over every
+    chain and record, per dim, computed on the device (diag.pooled_hist is the
+    definition; np.histogram(values, edges) bit for bit).  edges: a list of d
+    arrays of strictly increasing finite edges, at most 4 096 bins each, None
+    for a dim to skip.  {'counts': [int64 [B_k] or None per dim], 'outside':
+    int64 [d, 3]}: outside holds the draws below the first edge, above the last
+    one and NaN, so that a dim's counts and its row add up to N count.  One
+    pass over the window for dims that fit a workgroup's LDS together."""
+    first, count = self._window(first, count)
+    arrays, n_bins, flat = self._hist_args('trace_hist', edges)
+    counts = np.zeros(max(int(n_bins.sum()), 1), np.int64)
+    outside = np.zeros((self.dim, 3), np.int64)
+    i64p = _c.POINTER(_c.c_int64)
+    _lib.call('pbh_trace_hist', self._h, _c.c_int64(int(first)), _c.c_int64(int(count)),
+              _ip(n_bins), _dp(flat), counts.ctypes.data_as(i64p),
+              outside.ctypes.data_as(i64p))
+    ends = np.cumsum(n_bins)
+    return {'counts': [None if e is None else counts[end - b:end].copy()
+                       for e, b, end in zip(arrays, n_bins, ends)],
+            'outside': outside}
+
+  def trace_hist2d(self, edges, pairs, first=0, count=None):
+    """The joint histograms of pairs of dims over trace records [first, first
+    + count), pooled over every chain and record, computed on the device
+    (diag.pooled_hist2d is the definition; np.histogram2d with explicit edges
+    bit for bit): a list of int64 [B_a, B_b], one per (a, b) in pairs.  H[i, j]
+    counts the draws with x_a in bin i of dim a and x_b in bin j of dim b; a
+    draw with either value outside its edges, or NaN, is dropped.  edges as
+    trace_hist takes them; a pair has at most 16 384 cells; a == b is
+    allowed."""
+    first, count = self._window(first, count)
+    _, n_bins, flat = self._hist_args('trace_hist2d', edges)
+    pr = _i32(np.asarray(pairs, np.int64).reshape(-1, 2) if len(pairs) else np.zeros((0, 2)))
+    # The library refuses a pair it cannot count -- a dim outside [0, d) or
+    # without edges, more than PBH_HIST2D_MAX_CELLS cells -- with the message
+    # that names it, before it writes anything (hist2d_check_pairs runs ahead
+    # of the window check), so such a pair is passed on, not refused here.  The
+    # buffer does not lean on that order: a pair the library would refuse is
+    # given the most cells any pair may have.
+    max_cells = 16384   # PBH_HIST2D_MAX_CELLS
+    d = self.dim
+    shapes = [(int(n_bins[a]), int(n_bins[b])) if 0 <= a < d and 0 <= b < d else (0, 0)
+              for a, b in pr]
+    sizes = [ba * bb if 0 < ba * bb <= max_cells else max_cells for ba, bb in shapes]
+    counts = np.zeros(max(sum(sizes), 1), np.int64)
+    _lib.call('pbh_trace_hist2d', self._h, _c.c_int64(int(first)), _c.c_int64(int(count)),
+              _ip(n_bins), _dp(flat), _c.c_int32(pr.shape[0]),
+              _ip(pr if pr.size else np.zeros(2, np.int32)),
+              counts.ctypes.data_as(_c.POINTER(_c.c_int64)))
+    ends = np.cumsum(sizes)
+    return [counts[end - size:end].reshape(shape).copy()
+            for shape, size, end in zip(shapes, sizes, ends)]
+
   def rccl_allreduce_max(self, value):
     v = _c.c_double(float(value))
     _lib.call('pbh_rccl_allreduce_max', self._h, _c.byref(v))

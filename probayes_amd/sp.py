@@ -1548,6 +1548,96 @@ class Sampler:
         raise ValueError('trace_tran: ' + why)
     return diag.proposal_cov(self.trace_cov(first, count)['cov'], scale, eps)
 
+  def _hist_edges(self, bins, range, first, count):
+    """diag.hist_edges for the sampler's names: a list of edges, None for a
+    skipped name.  A range that is not given is the pooled minimum and maximum
+    of the window, which the device's select gives exactly."""
+    from probayes_amd import diag
+
+    def minmax():
+      res = self._eng.trace_quantile_pooled([0., 1.], first, count)
+      return {k: (res[0, i], res[1, i]) for i, k in enumerate(self.names)}
+
+    return diag.hist_edges(bins, range, list(self.names), minmax)
+
+  def trace_hist(self, bins=10, range=None, first=0, count=None, density=False):
+    """The posterior histogram of every name, pooled over every chain and every
+    record [first, first + count), computed by the engine from its device trace
+    (Engine.trace_hist) without copying the trace to the host: {name: (hist,
+    edges)}, each pair what np.histogram(the pooled values of name, bins, range,
+    density=density) returns, the counts bit for bit.  bins: an int, an edge
+    array, or {name: either} -- a name left out is skipped; range: (lo, hi),
+    {name: (lo, hi)} or None, the pooled minimum and maximum (diag.hist_edges
+    has the rules, NumPy's).  At most 4 096 bins a name.  Covers the sampler's
+    first block while the engine still holds it, as trace_quantile does."""
+    from probayes_amd import diag
+    first, count = self._device_window('trace_hist', first, count)
+    edges = self._hist_edges(bins, range, first, count)
+    if all(e is None for e in edges):
+      raise ValueError('trace_hist: bins names none of {}'.format(list(self.names)))
+    res = self._eng.trace_hist(edges, first, count)
+    return {k: (diag.hist_density(h, e) if density else h, e)
+            for k, h, e in zip(self.names, res['counts'], edges) if e is not None}
+
+  def trace_hist2d(self, x, y, bins=10, range=None, first=0, count=None, density=False):
+    """The joint posterior histogram of the names x and y -- the binned
+    replacement of their scatter plot -- pooled over every chain and every
+    record [first, first + count), computed by the engine from its device trace
+    (Engine.trace_hist2d): (H, xedges, yedges), what np.histogram2d(the pooled
+    values of x, those of y, bins, range, density=density) returns.  bins: an
+    int, [int, int], an edge array or [array, array]; range: [[xlo, xhi], [ylo,
+    yhi]] or None.  At most 16 384 cells.  Covers the sampler's first block
+    while the engine still holds it, as trace_quantile does."""
+    from probayes_amd import diag
+    first, count = self._device_window('trace_hist2d', first, count)
+    names = list(self.names)
+    for k in (x, y):
+      if k not in names:
+        raise ValueError('trace_hist2d: {!r} is not one of the names {}'.format(k, names))
+    try:
+      two = len(bins) == 2
+    except TypeError:
+      two = False
+    bx, by = (bins[0], bins[1]) if two else (bins, bins)
+    rx, ry = (None, None) if range is None else (range[0], range[1])
+    a, b = names.index(x), names.index(y)
+    if a != b:
+      per = self._hist_edges({x: bx, y: by}, {x: rx, y: ry}, first, count)
+      ex, ey = per[a], per[b]
+    else:
+      # one dim carries one set of edges: x against itself in its own bins
+      ex = self._hist_edges({x: bx}, {x: rx}, first, count)[a]
+      ey = self._hist_edges({y: by}, {y: ry}, first, count)[a]
+      if ex.tobytes() != ey.tobytes():
+        raise ValueError('trace_hist2d: {!r} against itself needs the same edges on both '
+                         'axes'.format(x))
+    edges = [None] * len(names)
+    edges[a], edges[b] = ex, ey
+    h = self._eng.trace_hist2d(edges, [(a, b)], first, count)[0]
+    h = diag.hist2d_density(h, ex, ey) if density else h.astype(float)
+    return h, ex, ey
+
+  def trace_corner(self, bins=10, range=None, first=0, count=None):
+    """The picture of the whole posterior in two device calls: every name's
+    histogram (trace_hist) and, in the same bins, the joint histogram of every
+    pair of names a before b (Engine.trace_hist2d): {'names': [...], 'hist':
+    {name: (counts, edges)}, 'hist2d': {(a, b): int64 [B_a, B_b]}} -- the panels
+    of a corner plot.  bins and range as trace_hist takes them; a pair has at
+    most 16 384 cells."""
+    first, count = self._device_window('trace_corner', first, count)
+    edges = self._hist_edges(bins, range, first, count)
+    names = [k for k, e in zip(self.names, edges) if e is not None]
+    if not names:
+      raise ValueError('trace_corner: bins names none of {}'.format(list(self.names)))
+    res = self._eng.trace_hist(edges, first, count)
+    at = [i for i, e in enumerate(edges) if e is not None]
+    pairs = [(a, b) for i, a in enumerate(at) for b in at[i + 1:]]
+    grids = self._eng.trace_hist2d(edges, pairs, first, count) if pairs else []
+    every = list(self.names)
+    return {'names': names,
+            'hist': {every[i]: (res['counts'][i], edges[i]) for i in at},
+            'hist2d': {(every[a], every[b]): g for (a, b), g in zip(pairs, grids)}}
+
   def trace_quantile_pooled(self, q, first=0, count=None):
     """The posterior quantiles q of every name, pooled over every chain and
     every record [first, first + count), computed by the engine from its
